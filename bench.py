@@ -3,12 +3,22 @@ crates/groth16-cli/src/lib.rs:57-70 (BASELINE.json configs[3] at one GPU,
 configs[4] on N > 1), plus G1 MSM scalar-point pairs/s at 2^20 (configs[1])
 and the 2^22 Fr NTT (configs[2]) on rank 0 of a one-GPU run.
 
-  python bench.py [--gpus 1] [--steps K] [--warmup W]
+  python bench.py [--gpus 1] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py --full ...            (every leg described below)
   python bench.py --gpus N ...          (starts its own N rank processes)
   torchrun --nproc-per-node N bench.py --gpus N ...
 
 A step = one full prove (quotient NTTs + 5 MSMs + host tail) with the proving
 key and the witness already resident in HBM.
+
+A plain run does what the headline figure needs and nothing else: GPU setup
+of the key and the witness, W warmup steps, K timed steps, the JSON line
+(metric, value, unit, ms_per_step, the proof).  --dump-outputs DIR also
+writes the last timed step's proof as DIR/*.npy (dump_outputs below).  Every
+other leg named here -- the phase profile, the serial-schedule roofline, the
+PCIe-inclusive proves, the MSM and NTT lines, the CPU baselines and oracle
+comparisons, the 2^24 anchor and its shards, the N > 1 alternatives, the
+`details` file -- runs only with --full.
 
   N = 1  the 2^20-constraint prove (configs[3]); its own timed proof is
          checked bit for bit against the C oracle (oracle/, all host cores)
@@ -798,12 +808,15 @@ VERBOSE_KEYS = ("phases_ms_total", "note", "timing", "cores_note", "kernel_timin
 
 
 def compact_line(rec, details_path):
-    """Write the full record to details_path and return the compact line."""
+    """Write the full record to details_path (None: a plain run, no file) and
+    return the compact line."""
+    where = None
     try:
-        os.makedirs(os.path.dirname(details_path), exist_ok=True)
-        with open(details_path, "w") as f:
-            json.dump(rec, f, indent=1)
-        where = os.path.relpath(details_path, ROOT)
+        if details_path is not None:
+            os.makedirs(os.path.dirname(details_path), exist_ok=True)
+            with open(details_path, "w") as f:
+                json.dump(rec, f, indent=1)
+            where = os.path.relpath(details_path, ROOT)
     except OSError as e:
         where = f"(not written: {e})"
 
@@ -829,6 +842,22 @@ def compact_line(rec, details_path):
         if isinstance(holder, dict):
             holder.pop(path[-1], None)
     return line
+
+
+def dump_outputs(out_dir, proof):
+    """--dump-outputs: what the timed path returned in its last step, the
+    Groth16 proof, as .npy arrays.  The inputs (key parameters, witness, r, s)
+    follow from --seed alone, so two builds run with the same arguments are
+    comparable output for output.
+      proof_words.npy       (102,) float64: the proof's 51 uint64 words (a: 13,
+                            b: 25, c: 13; Proof.words) as 32-bit halves, low
+                            half first -- exact in float64
+      proof_compressed.npy  (192,) float32: the bytes of serialize_compressed()"""
+    os.makedirs(out_dir, exist_ok=True)
+    words = np.ascontiguousarray(proof.words, dtype="<u8").view("<u4")
+    np.save(os.path.join(out_dir, "proof_words.npy"), words.astype(np.float64))
+    comp = np.frombuffer(proof.serialize_compressed(), dtype=np.uint8)
+    np.save(os.path.join(out_dir, "proof_compressed.npy"), comp.astype(np.float32))
 
 
 def spawn_ranks(n):
@@ -914,7 +943,18 @@ def main():
     ap.add_argument("--seed", type=int, default=DEFAULT_SEED)
     ap.add_argument("--schedule", type=int, choices=(0, 3), default=0,
                     help="prove stream schedule of the timed region (3: every kernel serial, for profilers)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (phase profile, serial-schedule roofline, "
+                         "PCIe-inclusive proves, configs[1] MSM, configs[2] NTT, CPU baselines, the 2^24 anchor "
+                         "and its shards; N > 1: msm_only, the quotient alternatives) and write --details; "
+                         "the --no-* switches and --anchor-log-n / --shard-scaling trim a full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes the last timed step's proof to DIR as .npy arrays (float64 / float32)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: setup, warmup, the timed steps, the line
+        args.no_cpu_baseline = args.no_msm = args.no_serial = args.no_pcie = True
+        args.anchor_log_n = 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
     if os.environ.get("ZK_BENCH_LAUNCH_ECHO"):   # CPU test of the launcher: no torch, no GPU
@@ -1091,16 +1131,20 @@ def main():
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    ctx.profile(True)
-    prof_steps = max(2, min(args.steps, 5))
-    for _ in range(prof_steps):
-        if step() != proof:
-            raise SystemExit("profiled proof differs from the timed one")
-    torch.cuda.synchronize()
-    prof = ctx.profile_read()
-    ctx.profile(False)
-    if dist:
-        dist.barrier()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, proof)
+    prof, prof_steps = None, 0
+    if args.full:
+        ctx.profile(True)
+        prof_steps = max(2, min(args.steps, 5))
+        for _ in range(prof_steps):
+            if step() != proof:
+                raise SystemExit("profiled proof differs from the timed one")
+        torch.cuda.synchronize()
+        prof = ctx.profile_read()
+        ctx.profile(False)
+        if dist:
+            dist.barrier()
     if dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1110,7 +1154,7 @@ def main():
     g1_pairs, g2_pairs = prove_msm_pairs(n)
     roofline = None
 
-    if world > 1:
+    if world > 1 and args.full:
         # PCIe-inclusive sharded proof: every rank gets only ITS witness slice
         # (zk_groth16_witness_ranges) from host memory, the drop-in
         # prove(pk, witness) split across the ranks
@@ -1210,7 +1254,9 @@ def main():
                                                             args.seed + 21)
             dist.barrier()
 
-    if rank == 0 and world == 1:
+    if world == 1 and not args.full:
+        dpk.free()
+    if rank == 0 and world == 1 and args.full:
         # the dominant kernel's own duration: the same proves, every kernel in
         # order on one stream (overlap would stretch its HIP-event span)
         serial_prof = None
@@ -1317,7 +1363,7 @@ def main():
                                 "note": "scalar-point pairs of the reference's 5 MSMs per proof (G1 10n+6, G2 3n+3) "
                                         "/ whole-job time per proof"},
             "roofline": roofline,
-            "phases_ms_total": phase_table(prof), "phases_proofs": prof_steps,
+            "phases_ms_total": phase_table(prof) if prof is not None else None, "phases_proofs": prof_steps,
             "proof_compressed": proof.serialize_compressed().hex(),
             "build_id": zkp.build_id(),
         }
@@ -1328,7 +1374,7 @@ def main():
             proj["gpu_over_projection"] = round(rec["value"] / proj["value"], 2)
         if world > 1 and log_n_total == 24 and args.seed == DEFAULT_SEED:
             rec["bit_exact_vs_oracle"] = rec["proof_compressed"] == ORACLE_2P24   # the pinned oracle proof
-        line = compact_line(rec, args.details)
+        line = compact_line(rec, args.details if args.full else None)
         sys.stdout.write(json.dumps(line) + "\n")   # one write: ranks share the launcher's stdout
         sys.stdout.flush()
     ctx.close()

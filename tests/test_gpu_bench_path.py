@@ -31,7 +31,7 @@ def _free_port():
 
 
 LOG_N, SEED = 12, 0x5EED0001
-ARGS = ["--gpus", "2", "--steps", "1", "--warmup", "0", "--total-log-n", str(LOG_N), "--seed", str(SEED),
+ARGS = ["--full", "--gpus", "2", "--steps", "1", "--warmup", "0", "--total-log-n", str(LOG_N), "--seed", str(SEED),
         "--cpu-sample-log-n", "10"]
 
 

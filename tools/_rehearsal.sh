@@ -14,7 +14,7 @@ cd $R
 export ZK_BENCH_DIST_BACKEND=gloo ZK_BENCH_DEVICE=0
 if [ "$L" = torchrun ]; then
   timeout -k 10 1000 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-    --master-port 29533 bench.py --gpus $N --total-log-n 24 > $O/rehearsal_${N}rank_2p24.json 2> $O/rehearsal_${N}rank_2p24.log
+    --master-port 29533 bench.py --full --gpus $N --total-log-n 24 > $O/rehearsal_${N}rank_2p24.json 2> $O/rehearsal_${N}rank_2p24.log
 else
-  timeout -k 10 1000 python3 bench.py --gpus $N --total-log-n 24 > $O/rehearsal_${N}rank_2p24.json 2> $O/rehearsal_${N}rank_2p24.log
+  timeout -k 10 1000 python3 bench.py --full --gpus $N --total-log-n 24 > $O/rehearsal_${N}rank_2p24.json 2> $O/rehearsal_${N}rank_2p24.log
 fi

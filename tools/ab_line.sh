@@ -9,7 +9,7 @@ rounds=$1; shift
 for i in $(seq $rounds); do
   for v in base "$@"; do
     lib=""; [ $v != base ] && lib=$PWD/zero-knowledge-proofs_amd/var_$v/libzkp_amd.so
-    ZK_AMD_LIB=$lib timeout -k 10 200 python -u bench.py --no-cpu-baseline --no-pcie --anchor-log-n 0 \
+    ZK_AMD_LIB=$lib timeout -k 10 200 python -u bench.py --full --no-cpu-baseline --no-pcie --anchor-log-n 0 \
       --steps 20 --warmup 5 --details gpurun_out/abl_${v}_$i.json > /dev/null 2>&1
     echo "== $v round $i"
     python3 tools/r6_cmp.py gpurun_out/abl_${v}_$i.json

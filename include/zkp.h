@@ -163,10 +163,13 @@ int zk_ctx_set_schedule(zk_ctx *ctx, int schedule);
  *                         one order against the other on one node; no
  *                         effect without a distributed quotient or under
  *                         schedule 3, where everything runs in order)
+ *   ZK_OPT_POINT_CHUNK    points per kernel launch and device buffer of the
+ *                         point decompression / validation calls (default
+ *                         2^20, >= 1)
  * (Test hooks -- the virtual-rank prove, the bare exchange, fault injection
  * -- live in a separate library, include/zkp_test.h.) */
 enum { ZK_OPT_QUOTIENT_PATH = 1, ZK_OPT_PROVE_WIN_C = 2, ZK_OPT_EXCHANGE_TIMEOUT_MS = 3,
-       ZK_OPT_DIST_QUOTIENT = 5, ZK_OPT_EXCHANGE_FIRST = 6 };
+       ZK_OPT_DIST_QUOTIENT = 5, ZK_OPT_EXCHANGE_FIRST = 6, ZK_OPT_POINT_CHUNK = 7 };
 int zk_ctx_set_option(zk_ctx *ctx, int option, int64_t value);
 
 /* ---------------------------------------------------------------- MSM --- */
@@ -366,6 +369,52 @@ int zk_proof_serialize_compressed(const zk_proof *proof, uint8_t out[192]);
  * curve with the flagged root, in the prime-order subgroup.  Anything else
  * -> ZK_ERR_ARG (ark's SerializationError). */
 int zk_proof_deserialize_compressed(const uint8_t in[192], zk_proof *out);
+
+/* ------------------------------------------------- points of a key file --- */
+/* The same compressed encoding for whole arrays of points, as a proving or
+ * verification key file holds them: 48 bytes per G1 and 96 per G2 point
+ * (x.c1 with the flag bits, then x.c0) instead of the 104 / 200 of the affine
+ * structs.  These calls replace ark CanonicalSerialize / CanonicalDeserialize
+ * (compressed, Validate::Yes) on G1Affine / G2Affine.  They have no reference
+ * counterpart at key level: the reference CLI writes JSON placeholders for
+ * its keys (crates/groth16-cli/src/lib.rs:157-219).
+ *
+ * What a decompressed or validated point can be, per point: the first check
+ * that fails, in the order of the proof decoder above. */
+typedef enum {
+  ZK_POINT_OK = 0,               /* valid (the identity included) */
+  ZK_POINT_ENCODING = 1,         /* compression flag clear; or the infinity flag with the sort
+                                    flag or any other x bit set (one identity encoding only) */
+  ZK_POINT_NOT_CANONICAL = 2,    /* a coordinate >= p */
+  ZK_POINT_NOT_ON_CURVE = 3,     /* x^3 + b has no square root / y^2 != x^3 + b */
+  ZK_POINT_NOT_IN_SUBGROUP = 4   /* [r]P != O */
+} zk_point_status;
+/* CanonicalSerialize::serialize_compressed of n points: 48 n bytes out.  Host
+ * only, no ctx; writes the encoding of whatever it is given (no validation). */
+int zk_g1_compress(const zk_g1_affine *pts, size_t n, uint8_t *out);
+/* Same for G2Affine: 96 n bytes out. */
+int zk_g2_compress(const zk_g2_affine *pts, size_t n, uint8_t *out);
+/* CanonicalDeserialize::deserialize_compressed (Validate::Yes) of n G1Affine
+ * on the GPU, one lane per point: square root, flagged sign, [r]P == O.
+ * status (n bytes of zk_point_status) and first_bad (the lowest failing
+ * index, n when there is none) may be NULL.  ZK_OK when every point is valid;
+ * ZK_ERR_ARG when any is not -- out (zeros for an invalid point), status and
+ * *first_bad are still filled; ZK_ERR_DEVICE on a HIP error.  n == 0 -> ZK_OK.
+ * The array crosses the GPU in chunks of ZK_OPT_POINT_CHUNK points. */
+int zk_g1_decompress(zk_ctx *ctx, const uint8_t *in, size_t n, zk_g1_affine *out, uint8_t *status,
+                     size_t *first_bad);
+/* Same for G2Affine (Fq2 square root). */
+int zk_g2_decompress(zk_ctx *ctx, const uint8_t *in, size_t n, zk_g2_affine *out, uint8_t *status,
+                     size_t *first_bad);
+/* The checks of Validate::Yes on n G1Affine already in affine form (what
+ * G1Affine::check does after an uncompressed read): coordinates < p, on the
+ * curve (else ZK_POINT_NOT_ON_CURVE), in the subgroup.  A set infinity byte is
+ * the identity whatever the coordinates hold.  Returns as the decompression
+ * does.  zk_pk_upload itself stays unchecked: a caller that does not trust its
+ * key runs this first. */
+int zk_g1_validate(zk_ctx *ctx, const zk_g1_affine *pts, size_t n, uint8_t *status, size_t *first_bad);
+/* Same for G2Affine. */
+int zk_g2_validate(zk_ctx *ctx, const zk_g2_affine *pts, size_t n, uint8_t *status, size_t *first_bad);
 
 /* -------------------------------------------------------------- verify --- */
 /* Host-only (no GPU): a handful of sequential pairings per call. */

@@ -44,6 +44,16 @@ int zk_test_pk_bases(zk_ctx *ctx, const zk_pk_dev *pk, int slot, int window, uin
                      uint64_t *words_out, size_t cap, size_t *count, size_t *nextras);
 /* The key's window plan and shard: win copies of c = win_c bits. */
 int zk_test_pk_info(const zk_pk_dev *pk, uint32_t *win, uint32_t *win_c, uint32_t *shard, uint32_t *nshards);
+/* The device square roots behind point decompression (csrc/points.hpp), one
+ * lane per element: in = n canonical Fq (6 words each), out = a canonical
+ * root where ok[i] = 1 (zeros where the input has none), largest[i] = the
+ * encodings' sort-flag predicate on that root (out > (p - 1) / 2).  Curve
+ * points never reach the rare branches (0, -1, roots with a zero
+ * coefficient, an Fq non-residue inside Fq2); these hooks do. */
+int zk_test_fq_sqrt(zk_ctx *ctx, const uint64_t *in, size_t n, uint64_t *out, uint8_t *ok, uint8_t *largest);
+/* Same in Fq2: 12 words per element (c0 then c1); largest looks at c1, or at
+ * c0 when c1 == 0. */
+int zk_test_fq2_sqrt(zk_ctx *ctx, const uint64_t *in, size_t n, uint64_t *out, uint8_t *ok, uint8_t *largest);
 
 #ifdef __cplusplus
 }

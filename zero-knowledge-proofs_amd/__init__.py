@@ -53,12 +53,20 @@ EXPORTS = (
     "zk_poly_evaluate_batch", "zk_synthetic_witness_dev", "zk_ctx_set_option", "zk_ctx_timeline_read",
     "zk_ctx_attach_exchange", "zk_groth16_witness_ranges", "zk_groth16_prove_partial_host",
     "zk_ctx_detach_exchange",
+    "zk_g1_compress", "zk_g2_compress", "zk_g1_decompress", "zk_g2_decompress",
+    "zk_g1_validate", "zk_g2_validate",
 )
 # include/zkp_test.h (libzkp_amd_test.so)
 TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fault_after_exchange",
-                "zk_test_pk_bases", "zk_test_pk_info")
+                "zk_test_pk_bases", "zk_test_pk_info", "zk_test_fq_sqrt", "zk_test_fq2_sqrt")
 ZK_OPT_QUOTIENT_PATH, ZK_OPT_PROVE_WIN_C, ZK_OPT_EXCHANGE_TIMEOUT_MS, ZK_OPT_DIST_QUOTIENT = 1, 2, 3, 5
 ZK_OPT_EXCHANGE_FIRST = 6
+ZK_OPT_POINT_CHUNK = 7
+# zk_point_status: what a decompressed / validated point can be
+ZK_POINT_OK, ZK_POINT_ENCODING, ZK_POINT_NOT_CANONICAL, ZK_POINT_NOT_ON_CURVE, ZK_POINT_NOT_IN_SUBGROUP = range(5)
+POINT_STATUS_TEXT = ("valid", "bad encoding flags", "coordinate not below p", "not on the curve",
+                     "not in the prime-order subgroup")
+G1_BYTES, G2_BYTES = 48, 96
 CSRC = os.path.join(_HERE, "csrc")
 
 
@@ -386,9 +394,10 @@ class Context:
         1 large-domain), ZK_OPT_PROVE_WIN_C (0 by size, 16, 22; keys made
         afterwards), ZK_OPT_EXCHANGE_TIMEOUT_MS (>= 1), ZK_OPT_DIST_QUOTIENT
         (-1 distributed when an exchange of the key's shape is attached, 0
-        replicated) or ZK_OPT_EXCHANGE_FIRST (0 MSMs start with the witness, 1
-        they wait for the distributed quotient).  Explicit path choices for
-        tests and A/B runs."""
+        replicated), ZK_OPT_EXCHANGE_FIRST (0 MSMs start with the witness, 1
+        they wait for the distributed quotient) or ZK_OPT_POINT_CHUNK (points
+        per launch of the decompress / validate calls, >= 1).  Explicit path
+        choices for tests and A/B runs."""
         _check(lib().zk_ctx_set_option(C.c_void_p(self._h), C.c_int(int(option)), C.c_int64(int(value))), self,
                "zk_ctx_set_option")
 
@@ -447,6 +456,51 @@ class Context:
                              C.c_size_t(len(scalars)), C.c_uint32(scalar_bits), _p(out))
         _check(rc, self, "zk_msm_g2")
         return out
+
+    # ---- points of a key file (ark CanonicalDeserialize, Validate::Yes) ----
+    def _decompress(self, name, data, enc, words):
+        if isinstance(data, np.ndarray):
+            buf = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        else:
+            buf = np.frombuffer(data, dtype=np.uint8)
+        if len(buf) % enc:
+            raise ValueError(f"{name}: {len(buf)} bytes is not a whole number of {enc}-byte points")
+        n = len(buf) // enc
+        out = np.zeros((n, words), dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8)
+        if n:
+            rc = getattr(lib(), name)(C.c_void_p(self._h), _p(buf), C.c_size_t(n), _p(out), _p(st), None)
+            if not (rc == ZK_ERR_ARG and st.any()):   # invalid points are reported by their status
+                _check(rc, self, name)
+        return out, st
+
+    def g1_decompress(self, data):
+        """zk_g1_decompress: 48 n bytes -> ((n, 13) uint64 affine words, n
+        uint8 zk_point_status).  An invalid point has a non-zero status and
+        zero words; nothing is raised for it."""
+        return self._decompress("zk_g1_decompress", data, G1_BYTES, G1_WORDS)
+
+    def g2_decompress(self, data):
+        """zk_g2_decompress: 96 n bytes -> ((n, 25) words, n statuses)."""
+        return self._decompress("zk_g2_decompress", data, G2_BYTES, G2_WORDS)
+
+    def _validate(self, name, arr, words):
+        a = np.ascontiguousarray(arr, dtype=np.uint64).reshape(-1, words)
+        st = np.zeros(len(a), dtype=np.uint8)
+        if len(a):
+            rc = getattr(lib(), name)(C.c_void_p(self._h), _p(a), C.c_size_t(len(a)), _p(st), None)
+            if not (rc == ZK_ERR_ARG and st.any()):
+                _check(rc, self, name)
+        return st
+
+    def g1_validate(self, arr):
+        """zk_g1_validate: (n, 13) affine words -> n uint8 zk_point_status
+        (coordinates < p, on the curve, in the prime-order subgroup)."""
+        return self._validate("zk_g1_validate", arr, G1_WORDS)
+
+    def g2_validate(self, arr):
+        """zk_g2_validate: (n, 25) affine words -> n statuses."""
+        return self._validate("zk_g2_validate", arr, G2_WORDS)
 
     # ---- NTT (ark-poly Radix2EvaluationDomain fft / ifft / coset) ----
     def ntt(self, data, inverse=False, coset=None):
@@ -682,6 +736,76 @@ class SetupParams:
         return p
 
 
+# ------------------------------------------------- points of a key ----
+def compress_g1(words):
+    """zk_g1_compress: (n, 13) affine words -> 48 n bytes (ark compressed
+    G1Affine; host only, does not validate)."""
+    a = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, G1_WORDS)
+    out = np.zeros(G1_BYTES * len(a), dtype=np.uint8)
+    if len(a):
+        _check(lib().zk_g1_compress(_p(a), C.c_size_t(len(a)), _p(out)), None, "zk_g1_compress")
+    return out.tobytes()
+
+
+def compress_g2(words):
+    """zk_g2_compress: (n, 25) affine words -> 96 n bytes."""
+    a = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, G2_WORDS)
+    out = np.zeros(G2_BYTES * len(a), dtype=np.uint8)
+    if len(a):
+        _check(lib().zk_g2_compress(_p(a), C.c_size_t(len(a)), _p(out)), None, "zk_g2_compress")
+    return out.tobytes()
+
+
+# every point of a key in file order: (field, group, is a single point)
+_PK_FIELDS = (("alpha_g1", 1, True), ("beta_g1", 1, True), ("delta_g1", 1, True), ("beta_g2", 2, True),
+              ("delta_g2", 2, True), ("a_g1", 1, False), ("b_g1", 1, False), ("b_g2", 2, False),
+              ("ic_g1", 1, False), ("h_g1", 1, False))
+_VK_FIELDS = (("alpha_g1", 1, True), ("beta_g2", 2, True), ("gamma_g2", 2, True), ("delta_g2", 2, True),
+              ("ic_g1", 1, False))
+
+
+class InvalidPoint(Exception):
+    """A key point failed decompression / validation: field, index, zk_point_status."""
+
+    def __init__(self, field, index, status):
+        self.field, self.index, self.status = field, int(index), int(status)
+        super().__init__(f"{field}[{self.index}]: {POINT_STATUS_TEXT[self.status]}")
+
+
+def _check_fields(ctx, fields, compressed):
+    """fields: [(name, group, data)] in key order, data = affine words, or
+    compressed bytes when `compressed`.  Neighbouring fields of one group go
+    through the GPU in one call.  Returns the affine words per field; raises
+    InvalidPoint for the first bad point in key order."""
+    out, i = [], 0
+    while i < len(fields):
+        j = i
+        while j < len(fields) and fields[j][1] == fields[i][1]:
+            j += 1
+        g1 = fields[i][1] == 1
+        if compressed:
+            counts = [len(f[2]) // (G1_BYTES if g1 else G2_BYTES) for f in fields[i:j]]
+            words, st = (ctx.g1_decompress if g1 else ctx.g2_decompress)(b"".join(f[2] for f in fields[i:j]))
+        else:
+            parts = [np.asarray(f[2], dtype=np.uint64).reshape(-1, G1_WORDS if g1 else G2_WORDS) for f in fields[i:j]]
+            counts = [len(a) for a in parts]
+            words = np.concatenate(parts)
+            st = (ctx.g1_validate if g1 else ctx.g2_validate)(words)
+        lo = 0
+        for (name, _, _), k in zip(fields[i:j], counts):
+            bad = np.flatnonzero(st[lo:lo + k])
+            if len(bad):
+                raise InvalidPoint(name, bad[0], st[lo + bad[0]])
+            out.append(words[lo:lo + k])
+            lo += k
+        i = j
+    return out
+
+
+def _key_fields(key, table):
+    return [(nm, g, key.point(nm).reshape(1, -1) if single else getattr(key, nm)) for nm, g, single in table]
+
+
 class ProvingKey:
     """crates/groth16-setup/src/lib.rs:27-52 (host arrays, canonical affine)."""
 
@@ -708,6 +832,17 @@ class ProvingKey:
     def point(self, name):
         """alpha_g1 / beta_g1 / delta_g1 / beta_g2 / delta_g2 as uint64 words."""
         return np.array(getattr(self.s, name).w, dtype=np.uint64)
+
+    def validate(self, ctx=None):
+        """ark's Validate::Yes on every point of the key, on the GPU: the five
+        single points and the five base vectors must be canonical, on their
+        curve and in the prime-order subgroup.  Raises SetupError naming the
+        field, the index and the reason ("b_g2[17]: not in the prime-order
+        subgroup").  Uploading a key never checks it; this does."""
+        try:
+            _check_fields(ctx or default_context(), _key_fields(self, _PK_FIELDS), False)
+        except InvalidPoint as e:
+            raise SetupError(str(e)) from None
 
     def upload(self, ctx, shard=0, nshards=1):
         return DeviceProvingKey.upload(ctx, self, shard, nshards)
@@ -739,6 +874,13 @@ class VerificationKey:
 
     def point(self, name):
         return np.array(getattr(self.s, name).w, dtype=np.uint64)
+
+    def validate(self, ctx=None):
+        """ProvingKey.validate for the four single points and ic_g1."""
+        try:
+            _check_fields(ctx or default_context(), _key_fields(self, _VK_FIELDS), False)
+        except InvalidPoint as e:
+            raise SetupError(str(e)) from None
 
 
 class DeviceProvingKey:
@@ -1116,7 +1258,17 @@ class BatchVerifier:
 #   verification key: b"ZKAMDVK1", u64 num_public, ic_len, alpha_g1,
 #                 beta_g2, gamma_g2, delta_g2, ic_g1[ic_len]
 #   proof:        the 192-byte ark compressed encoding (Proof::serialize_compressed)
+# Compressed key files hold every point in the ark / zcash compressed encoding
+# (48 bytes per G1, 96 per G2 point: under half the size) and are decompressed
+# -- which validates every point -- on the GPU when they are loaded:
+#   proving key:  b"ZKAMDPK2", the same u64 x 9 header, alpha_g1, beta_g1,
+#                 delta_g1 (48 bytes each), beta_g2, delta_g2 (96 each), a_g1,
+#                 b_g1, b_g2, ic_g1, h_g1 compressed, zero bytes up to a
+#                 multiple of 8, then the CSR section byte for byte as above
+#   verification key: b"ZKAMDVK2", u64 num_public, ic_len, alpha_g1 (48),
+#                 beta_g2, gamma_g2, delta_g2 (96 each), ic_g1 compressed
 _PK_MAGIC, _VK_MAGIC = b"ZKAMDPK1", b"ZKAMDVK1"
+_PK2_MAGIC, _VK2_MAGIC = b"ZKAMDPK2", b"ZKAMDVK2"
 
 
 def _u64s(f, k):
@@ -1126,16 +1278,44 @@ def _u64s(f, k):
     return a
 
 
-def save_proving_key(pk, path):
+def _read_exact(f, k):
+    b = f.read(k)
+    if len(b) != k:
+        raise ValueError("truncated key file")
+    return b
+
+
+def _write_compressed(f, key, table):
+    for nm, group, single in table:
+        words = key.point(nm) if single else getattr(key, nm)
+        f.write((compress_g1 if group == 1 else compress_g2)(words))
+
+
+def _read_compressed(f, path, ctx, table, counts):
+    """The compressed points of a key file, table order -> affine words per
+    field, decompressed (and so validated) on the GPU."""
+    fields = [(nm, group, _read_exact(f, k * (G1_BYTES if group == 1 else G2_BYTES)))
+              for (nm, group, _), k in zip(table, counts)]
+    try:
+        return _check_fields(ctx or default_context(), fields, True)
+    except InvalidPoint as e:
+        raise ValueError(f"{path}: {e}") from None
+
+
+def save_proving_key(pk, path, compressed=False):
     with open(path, "wb") as f:
-        f.write(_PK_MAGIC)
+        f.write(_PK2_MAGIC if compressed else _PK_MAGIC)
         csr = pk.qap.csr
         np.array([pk.qap.num_variables, pk.qap.domain_size, pk.num_public, csr.num_constraints,
                   len(pk.a_g1), len(pk.b_g1), len(pk.b_g2), len(pk.ic_g1), len(pk.h_g1)], dtype="<u8").tofile(f)
-        for nm in ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2"):
-            pk.point(nm).astype("<u8").tofile(f)
-        for arr in (pk.a_g1, pk.b_g1, pk.b_g2, pk.ic_g1, pk.h_g1):
-            np.ascontiguousarray(arr, dtype="<u8").tofile(f)
+        if compressed:
+            _write_compressed(f, pk, _PK_FIELDS)
+            f.write(b"\0" * (-f.tell() % 8))
+        else:
+            for nm in ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2"):
+                pk.point(nm).astype("<u8").tofile(f)
+            for arr in (pk.a_g1, pk.b_g1, pk.b_g2, pk.ic_g1, pk.h_g1):
+                np.ascontiguousarray(arr, dtype="<u8").tofile(f)
         for rp, col, val in csr.mats:
             nnz = len(col)
             np.array([nnz, val is not None], dtype="<u8").tofile(f)
@@ -1147,14 +1327,25 @@ def save_proving_key(pk, path):
                 np.ascontiguousarray(val, dtype="<u8").tofile(f)
 
 
-def load_proving_key(path):
+def load_proving_key(path, ctx=None, validate=False):
+    """Read a ZKAMDPK1 or ZKAMDPK2 file (picked by its magic).  A compressed
+    file is decompressed on the GPU of `ctx` (default_context() when None),
+    which validates every point; an uncompressed one is read as it is, and
+    checked by ProvingKey.validate(ctx) only with validate=True.  An invalid
+    point raises ValueError("<path>: <field>[<index>]: <reason>")."""
     with open(path, "rb") as f:
-        if f.read(8) != _PK_MAGIC:
+        magic = f.read(8)
+        if magic not in (_PK_MAGIC, _PK2_MAGIC):
             raise ValueError(f"{path}: not a proving key file")
         V, n, npub, nc, la, lb, lb2, lic, lh = (int(x) for x in _u64s(f, 9))
-        pts = [_u64s(f, G1_WORDS) for _ in range(3)] + [_u64s(f, G2_WORDS) for _ in range(2)]
-        arrs = [_u64s(f, k * w).reshape(k, w) for k, w in
-                ((la, G1_WORDS), (lb, G1_WORDS), (lb2, G2_WORDS), (lic, G1_WORDS), (lh, G1_WORDS))]
+        if magic == _PK2_MAGIC:
+            got = _read_compressed(f, path, ctx, _PK_FIELDS, (1, 1, 1, 1, 1, la, lb, lb2, lic, lh))
+            pts, arrs = [a.reshape(-1) for a in got[:5]], got[5:]
+            _read_exact(f, -f.tell() % 8)
+        else:
+            pts = [_u64s(f, G1_WORDS) for _ in range(3)] + [_u64s(f, G2_WORDS) for _ in range(2)]
+            arrs = [_u64s(f, k * w).reshape(k, w) for k, w in
+                    ((la, G1_WORDS), (lb, G1_WORDS), (lb2, G2_WORDS), (lic, G1_WORDS), (lh, G1_WORDS))]
         mats = []
         for _ in range(3):
             nnz, has_val = (int(x) for x in _u64s(f, 2))
@@ -1175,27 +1366,47 @@ def load_proving_key(path):
         field = getattr(pk.s, nm)
         for i, w in enumerate(words):
             field.w[i] = int(w)
+    if validate and magic == _PK_MAGIC:
+        _validate_loaded(pk, path, ctx)
     return pk
 
 
-def save_verification_key(vk, path):
+def _validate_loaded(key, path, ctx):
+    try:
+        key.validate(ctx)
+    except SetupError as e:
+        raise ValueError(f"{path}: {e}") from None
+
+
+def save_verification_key(vk, path, compressed=False):
     with open(path, "wb") as f:
-        f.write(_VK_MAGIC)
+        f.write(_VK2_MAGIC if compressed else _VK_MAGIC)
         np.array([vk.num_public, len(vk.ic_g1)], dtype="<u8").tofile(f)
+        if compressed:
+            _write_compressed(f, vk, _VK_FIELDS)
+            return
         for nm in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2"):
             vk.point(nm).astype("<u8").tofile(f)
         np.ascontiguousarray(vk.ic_g1, dtype="<u8").tofile(f)
 
 
-def load_verification_key(path):
+def load_verification_key(path, ctx=None, validate=False):
+    """Read a ZKAMDVK1 or ZKAMDVK2 file; see load_proving_key."""
     with open(path, "rb") as f:
-        if f.read(8) != _VK_MAGIC:
+        magic = f.read(8)
+        if magic not in (_VK_MAGIC, _VK2_MAGIC):
             raise ValueError(f"{path}: not a verification key file")
         npub, lic = (int(x) for x in _u64s(f, 2))
-        pts = [_u64s(f, G1_WORDS)] + [_u64s(f, G2_WORDS) for _ in range(3)]
-        ic = _u64s(f, lic * G1_WORDS).reshape(lic, G1_WORDS)
+        if magic == _VK2_MAGIC:
+            got = _read_compressed(f, path, ctx, _VK_FIELDS, (1, 1, 1, 1, lic))
+            pts, ic = [a.reshape(-1) for a in got[:4]], got[4]
+        else:
+            pts = [_u64s(f, G1_WORDS)] + [_u64s(f, G2_WORDS) for _ in range(3)]
+            ic = _u64s(f, lic * G1_WORDS).reshape(lic, G1_WORDS)
     vk = VerificationKey.from_points(*pts, ic)
     vk.num_public = vk.s.num_public = npub
+    if validate and magic == _VK_MAGIC:
+        _validate_loaded(vk, path, ctx)
     return vk
 
 

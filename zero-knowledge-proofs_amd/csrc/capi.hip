@@ -590,3 +590,15 @@ int zk_proof_serialize_compressed(const zk_proof* proof, uint8_t out[192]) {
   return ZK_OK;
 }
 
+// whole arrays of points (key files): the same encoder, no validation
+int zk_g1_compress(const zk_g1_affine* pts, size_t n, uint8_t* out) {
+  if (n && (!pts || !out)) return ZK_ERR_ARG;
+  for (size_t i = 0; i < n; i++) serialize_g1_compressed(pts[i], out + 48 * i);
+  return ZK_OK;
+}
+int zk_g2_compress(const zk_g2_affine* pts, size_t n, uint8_t* out) {
+  if (n && (!pts || !out)) return ZK_ERR_ARG;
+  for (size_t i = 0; i < n; i++) serialize_g2_compressed(pts[i], out + 96 * i);
+  return ZK_OK;
+}
+

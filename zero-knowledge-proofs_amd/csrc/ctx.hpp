@@ -65,6 +65,7 @@ struct zk_ctx {
   int dist_quotient = -1;                      // -1 distributed when an exchange of the key's shape
                                                // is attached, 0 never (each rank the whole quotient)
   int exchange_first = 0;                      // 1: distributed proofs run the quotient before the MSMs
+  size_t point_chunk = (size_t)1 << 20;        // points per launch of the decompress / validate calls
 
   zk::NttDomain& domain(uint32_t log_n);
 };

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "points.hpp"
 #include "../../include/zkp_test.h"
 
 namespace zk {
@@ -91,7 +92,82 @@ int zk_test_pk_bases(zk_ctx* ctx, const zk_pk_dev* pk, int slot, int window, uin
   })
 }
 
-int zk_test_pk_info(const zk_pk_dev* pk, uint32_t* win, uint32_t* win_c, uint32_t* shard, uint32_t* nshards) {
+// ---- the square roots of points.hpp on their own ---------------------------
+namespace zk {
+// K = 1: Fq, K = 2: Fq2 (c0 then c1); canonical words in and out
+template <int K>
+__global__ void __launch_bounds__(128) k_test_sqrt(const uint64_t* __restrict__ in, size_t n,
+                                                   uint64_t* __restrict__ out, uint8_t* __restrict__ ok,
+                                                   uint8_t* __restrict__ largest) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Fq a[K], r[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    Fq c;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+      const uint64_t w = in[6 * (K * i + k) + j];
+      c.v[2 * j] = (uint32_t)w;
+      c.v[2 * j + 1] = (uint32_t)(w >> 32);
+    }
+    a[k] = pt_to_mont(c);
+  }
+  bool good;
+  if constexpr (K == 1) {
+    good = pt_fq_sqrt(a[0], r[0]);
+  } else {
+    Fq2 root;
+    good = pt_fq2_sqrt(Fq2{a[0], a[1]}, root);
+    r[0] = root.c0;
+    r[1] = root.c1;
+  }
+#pragma unroll
+  for (int k = 0; k < K; k++) r[k] = good ? pt_from_mont(r[k]) : fp_zero<FqParams>();
+  bool big;
+  if constexpr (K == 1) big = pt_fq_largest(r[0]);
+  else big = pt_fq2_largest(Fq2{r[0], r[1]});
+#pragma unroll
+  for (int k = 0; k < K; k++)
+#pragma unroll
+    for (int j = 0; j < 6; j++)
+      out[6 * (K * i + k) + j] = (uint64_t)r[k].v[2 * j] | ((uint64_t)r[k].v[2 * j + 1] << 32);
+  ok[i] = good ? 1 : 0;
+  largest[i] = (good && big) ? 1 : 0;
+}
+
+template <int K>
+int test_sqrt(zk_ctx* ctx, const uint64_t* in, size_t n, uint64_t* out, uint8_t* ok, uint8_t* largest) {
+  if (!n) return ZK_OK;
+  const size_t words = 6 * K * n;
+  DevBuf d_in, d_out, d_ok, d_big;
+  d_in.ensure(8 * words);
+  d_out.ensure(8 * words);
+  d_ok.ensure(n);
+  d_big.ensure(n);
+  hipStream_t st = ctx->stream;
+  ZK_HIP(hipMemcpyAsync(d_in.p, in, 8 * words, hipMemcpyHostToDevice, st));
+  k_test_sqrt<K><<<ceil_div(n, 128), 128, 0, st>>>(d_in.as<uint64_t>(), n, d_out.as<uint64_t>(), d_ok.as<uint8_t>(),
+                                                   d_big.as<uint8_t>());
+  ZK_LAUNCH_CHECK();
+  ZK_HIP(hipMemcpyAsync(out, d_out.p, 8 * words, hipMemcpyDeviceToHost, st));
+  ZK_HIP(hipMemcpyAsync(ok, d_ok.p, n, hipMemcpyDeviceToHost, st));
+  ZK_HIP(hipMemcpyAsync(largest, d_big.p, n, hipMemcpyDeviceToHost, st));
+  ZK_HIP(hipStreamSynchronize(st));
+  return ZK_OK;
+}
+}  // namespace zk
+
+int zk_test_fq_sqrt(zk_ctx* ctx, const uint64_t* in, size_t n, uint64_t* out, uint8_t* ok, uint8_t* largest) {
+  if (!ctx || (n && (!in || !out || !ok || !largest))) return ZK_ERR_ARG;
+  ZK_TGUARD(ctx, { return test_sqrt<1>(ctx, in, n, out, ok, largest); })
+}
+int zk_test_fq2_sqrt(zk_ctx* ctx, const uint64_t* in, size_t n, uint64_t* out, uint8_t* ok, uint8_t* largest) {
+  if (!ctx || (n && (!in || !out || !ok || !largest))) return ZK_ERR_ARG;
+  ZK_TGUARD(ctx, { return test_sqrt<2>(ctx, in, n, out, ok, largest); })
+}
+
+int zk_test_pk_info(const zk_pk_dev* pk,uint32_t* win, uint32_t* win_c, uint32_t* shard, uint32_t* nshards) {
   if (!pk || !win || !win_c || !shard || !nshards) return ZK_ERR_ARG;
   *win = (uint32_t)pk->win;
   *win_c = (uint32_t)pk->win_c;

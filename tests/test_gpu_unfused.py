@@ -59,6 +59,33 @@ def test_three_window_plan_matches_oracle(zkp, oracle, log_n):
         _prove_vs_oracle(ctx, zkp, oracle, log_n)
 
 
+def test_three_window_plan_all_ones_witness(zkp, oracle):
+    """x = y = z = 1 in every row under the 3-window plan: the chunks are 4
+    entries, so the one giant bucket of every MSM spans hundreds of chunks
+    while the buckets outnumber the chunks.  The by-boundary fixup must count
+    that bucket exactly once -- once per G2 lane pair, not per lane -- and
+    hand it to the merge; the proof must match the oracle."""
+    import pyref
+    n = 1 << 10
+    rng = pyref.SplitMix64(4242)
+    params = [rng.fr() for _ in range(5)]
+    r, s = rng.fr(), rng.fr()
+    qap = zkp.QAP(zkp.CSRMatrices.synthetic(n))
+    csr_o = oracle.CSR.synthetic(n)
+    z = np.zeros((3 * n + 1, 4), dtype=np.uint64)
+    z[:, 0] = 1
+    rc, opk, _ = oracle.setup(csr_o, params, 1, nthreads=8)
+    assert rc == 0
+    rc, want = oracle.prove(opk, csr_o, z, 1, r, s)
+    assert rc == 0
+    with zkp.Context(0) as ctx:
+        ctx.set_option(zkp.ZK_OPT_PROVE_WIN_C, 22)
+        dpk = U.pk_from_oracle(zkp, opk, qap, 1).upload(ctx)
+        got = zkp.Prover.prove(dpk, zkp.Witness(z, 1), r=r, s=s)
+        dpk.free()
+    assert np.array_equal(got.words, want)
+
+
 def test_options_reject_unknown_values(zkp):
     with zkp.Context(0) as ctx:
         # 4: the old fault-injection option, now only in libzkp_amd_test.so

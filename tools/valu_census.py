@@ -16,7 +16,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = {"k_msm_accum<G1>": "_ZN2zk11k_msm_accumINS_2G1EEEvNS_8SegBasesINT_1AEEEjPKjS7_S7_jjPNS3_1XES9_",
-           "k_msm_accum_pair (G2)": "_ZN2zk16k_msm_accum_pairENS_8SegBasesI6AffineI3Fq2EEEjPKjS6_S6_jjP4XYZZIS2_ES9_"}
+           "k_msm_accum<G2>": "_ZN2zk11k_msm_accumINS_2G2EEEvNS_8SegBasesINT_1AEEEjPKjS7_S7_jjPNS3_1XES9_"}
 
 CLASSES = [
     ("v_mad_u64_u32 (limb products)", r"^v_mad_u64_u32"),

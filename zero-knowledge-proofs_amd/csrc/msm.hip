@@ -156,32 +156,149 @@ struct EntQ {
   }
 };
 
-// Thread t owns sorted entries [tK, tK+K).  One mixed add per entry (uniform
+// tuning builds: -DZK_ACCUM_WPE=w asks for >= w waves per SIMD (register
+// cap) on both accumulates, ZK_ACCUM_G1_WPE / ZK_ACCUM_G2_WPE on one of them;
+// ZK_ACCUM_G1_WAVES / ZK_ACCUM_G2_WAVES size the launch for that many waves
+// per SIMD, so that a full accumulate round leaves registers for other
+// streams' kernels (quotient, sorts) on every SIMD.  0: no cap.
+#ifndef ZK_ACCUM_WPE
+#define ZK_ACCUM_WPE 0
+#endif
+#ifndef ZK_ACCUM_G1_WPE
+#define ZK_ACCUM_G1_WPE ZK_ACCUM_WPE
+#endif
+#ifndef ZK_ACCUM_G2_WPE
+#define ZK_ACCUM_G2_WPE ZK_ACCUM_WPE
+#endif
+#ifndef ZK_ACCUM_G1_WAVES
+#define ZK_ACCUM_G1_WAVES 0
+#endif
+#ifndef ZK_ACCUM_G2_WAVES
+#define ZK_ACCUM_G2_WAVES 0
+#endif
+
+// One point of a wave moved to every lane: from lane d (XOR = false) or from
+// the lane d away in the butterfly (XOR = true).
+template <bool XOR, class X>
+ZK_DI X shfl_point(const X& v, int d) {
+  constexpr int NW = sizeof(X) / 4;
+  X o;
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(&v);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(&o);
+#pragma unroll
+  for (int k = 0; k < NW; k++) dst[k] = XOR ? __shfl_xor(src[k], d) : __shfl(src[k], d);
+  return o;
+}
+
+// -------------------------------------------------------- lane layout ---
+// How a curve's points sit on the lanes of a wave.  The kernels of every
+// phase but the merge are written once over Lanes<C>; a "unit" is the N
+// adjacent lanes that own one point in the accumulate, the fixup, the combine
+// and the serial part of the row/column sums:
+//   G1  one lane per point, the point whole in its registers;
+//   G2  a lane pair per point (Fq2h, ff.hpp): lane 2j holds the c0 and lane
+//       2j + 1 the c1 coefficient of every Fq2 coordinate -- 48 VGPRs per
+//       lane instead of 96 -- and the two read and write the two 48-byte
+//       halves of each coordinate.  The unit's lanes take every branch together.
+// The latency-bound ends of the reductions (the wave tail of a row/column
+// sum, the quantities) split each add over 4 lanes that hold the same
+// operands (add4: curve.hpp's lane-quad add for G1, its lane-duo add -- two
+// lane pairs -- for G2).
+// wave_tail: the wave's 32 unit points (G1: the sums of lanes l and l + 32,
+// the caller's last single-lane step; G2: its 32 lane pairs) summed by add4
+// in 5 rounds -- 16 adds (lanes 4j .. 4j + 3 take units 2j and 2j + 1), then
+// 8, 4, 2, 1 across lanes 32 .. 4 apart -- instead of 5 more butterfly steps
+// on units: a quad add issues about a third of a single-lane add's
+// instructions, a duo add has half the pair add's dependent products, and
+// these steps are the latency-bound tail of every sum.  The total is in
+// lanes 0-3.
+template <class C>
+struct Lanes;
+template <>
+struct Lanes<G1> {
+  using P = XYZZ<Fq>;     // a point in registers
+  using B = Affine<Fq>;   // an affine base in registers
+  static constexpr uint32_t N = 1;       // lanes per point
+  static constexpr uint32_t PARK = 1;    // lanes of a wave that park its 4-lane total in the LDS tree
+  static constexpr uint32_t XOR32 = 1;   // single-lane steps (lanes l + 32 onto l) before the wave tail
+  static constexpr bool TERM_AHEAD = true;   // k_msm_quant: where a term is loaded
+  static constexpr int ACCUM_WPE = ZK_ACCUM_G1_WPE, ACCUM_WAVES = ZK_ACCUM_G1_WAVES;
+  static ZK_DI P ld(const G1X* p) { return ld_vec(p); }
+  static ZK_DI void st(G1X* p, const P& a) { st_vec(p, a); }
+  static ZK_DI B ld_aff(const G1A* p) { return ld_vec(p); }
+  static ZK_DI bool lead() { return true; }   // the unit's lane that does its side effects
+  static ZK_DI P wave_tail(const P& v) {
+    const int j = (threadIdx.x & 63) >> 2;
+    P t;
+#pragma unroll 1
+    for (int it = 0; it < 5; it++) {
+      P a, b;
+      if (it == 0) {
+        a = shfl_point<false>(v, 2 * j);
+        b = shfl_point<false>(v, 2 * j + 1);
+      } else {
+        a = t;
+        b = shfl_point<true>(t, 64 >> it);
+      }
+      t = xyzz_add_quad(a, b);
+    }
+    return t;
+  }
+  static ZK_DI P add4(const P& p, const P& q) { return xyzz_add_quad(p, q); }
+};
+template <>
+struct Lanes<G2> {
+  using P = XYZZ<Fq2h>;
+  using B = Affine<Fq2h>;
+  static constexpr uint32_t N = 2;
+  static constexpr uint32_t PARK = 4;
+  static constexpr uint32_t XOR32 = 0;
+  static constexpr bool TERM_AHEAD = false;
+  static constexpr int ACCUM_WPE = ZK_ACCUM_G2_WPE, ACCUM_WAVES = ZK_ACCUM_G2_WAVES;
+  static ZK_DI P ld(const G2X* p) {
+    const Fq* q = reinterpret_cast<const Fq*>(p) + pair_half();
+    return {{ld_vec(q + 0)}, {ld_vec(q + 2)}, {ld_vec(q + 4)}, {ld_vec(q + 6)}};
+  }
+  static ZK_DI void st(G2X* p, const P& a) {
+    Fq* q = reinterpret_cast<Fq*>(p) + pair_half();
+    st_vec(q + 0, a.X.v);
+    st_vec(q + 2, a.Y.v);
+    st_vec(q + 4, a.ZZ.v);
+    st_vec(q + 6, a.ZZZ.v);
+  }
+  static ZK_DI B ld_aff(const G2A* p) {
+    const Fq* q = reinterpret_cast<const Fq*>(p) + pair_half();
+    return {{ld_vec(q)}, {ld_vec(q + 2)}};
+  }
+  static ZK_DI bool lead() { return !pair_half(); }
+  template <int K>
+  static ZK_DI P bcast(const P& v) {
+    return {duo_bcast<K>(v.X), duo_bcast<K>(v.Y), duo_bcast<K>(v.ZZ), duo_bcast<K>(v.ZZZ)};
+  }
+  static ZK_DI P wave_tail(const P& v) {
+    P t;
+#pragma unroll 1
+    for (int it = 0; it < 5; it++) {
+      P a, b;
+      if (it == 0) {
+        a = bcast<0>(v);
+        b = bcast<1>(v);
+      } else {
+        a = t;
+        b = shfl_point<true>(t, 64 >> it);
+      }
+      t = xyzz_add_duo(a, b);
+    }
+    return t;
+  }
+  static ZK_DI P add4(const P& p, const P& q) { return xyzz_add_duo(p, q); }
+};
+
+// Unit t owns sorted entries [tK, tK+K).  One mixed add per entry (uniform
 // across the wave); at a bucket change the finished run is flushed:
 //   complete bucket                        -> buckets[g]
-//   run begun by an earlier thread (head)   -> partials[2t]
-//   run continued by a later thread (tail)  -> partials[2t+1]
-// tuning builds: -DZK_ACCUM_WPE=w asks for >= w waves per SIMD (register cap)
-#ifdef ZK_ACCUM_WPE
-#define ZK_ACCUM_ATTR __attribute__((amdgpu_waves_per_eu(ZK_ACCUM_WPE)))
-#else
-#define ZK_ACCUM_ATTR
-#endif
-// A/B builds: register caps on the accumulates (ZK_ACCUM_G1_WPE /
-// ZK_ACCUM_G2_WPE waves per SIMD worth of registers) with the launch sized
-// for ZK_ACCUM_G1_WAVES / ZK_ACCUM_G2_WAVES waves per SIMD, so that a full
-// accumulate round leaves registers for other streams' kernels (quotient,
-// sorts) on every SIMD
-#ifdef ZK_ACCUM_G1_WPE
-#define ZK_ACCUM_G1_ATTR __attribute__((amdgpu_waves_per_eu(ZK_ACCUM_G1_WPE)))
-#else
-#define ZK_ACCUM_G1_ATTR ZK_ACCUM_ATTR
-#endif
-#ifdef ZK_ACCUM_G2_WPE
-#define ZK_ACCUM_G2_ATTR __attribute__((amdgpu_waves_per_eu(ZK_ACCUM_G2_WPE)))
-#else
-#define ZK_ACCUM_G2_ATTR ZK_ACCUM_ATTR
-#endif
+//   run begun by an earlier unit (head)     -> partials[2t]
+//   run continued by a later unit (tail)    -> partials[2t+1]
 template <class A>
 struct SegBases {
   const char* p[MSM_MAXSEG];
@@ -198,20 +315,18 @@ ZK_DI const A* seg_base(const SegBases<A>& sb, uint32_t seg, uint32_t i) {
 }
 
 template <class C>
-__global__ void __launch_bounds__(128) ZK_ACCUM_G1_ATTR k_msm_accum(SegBases<typename C::A> sb, uint32_t segshift,
-                                                   const uint32_t* __restrict__ ent,
-                                                   const uint32_t* __restrict__ key,
-                                                   const uint32_t* __restrict__ off, uint32_t G, uint32_t T,
-                                                   typename C::X* __restrict__ buckets,
-                                                   typename C::X* __restrict__ partials) {
-  using X = typename C::X;
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(Lanes<C>::ACCUM_WPE)))
+k_msm_accum(SegBases<typename C::A> sb, uint32_t segshift, const uint32_t* __restrict__ ent,
+            const uint32_t* __restrict__ key, const uint32_t* __restrict__ off, uint32_t G, uint32_t T,
+            typename C::X* __restrict__ buckets, typename C::X* __restrict__ partials) {
+  using L = Lanes<C>;
+  const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) / L::N;
   const uint32_t M = off[G];  // grouped entries (known on device only)
   const uint32_t K = chunk_len(M, T);
   const uint32_t start = t * K;
-  if (t >= T || start >= M) return;
+  if (t >= T || start >= M) return;   // uniform over the unit
   const uint32_t end = min(start + K, M);
-  X acc;
+  typename L::P acc;
   xyzz_set_inf(acc);
   uint32_t cur = key[start], run_start = start;
   __shared__ uint32_t entq_lds[2 * ENTQ_LDS_WORDS];   // 128 threads = 2 waves
@@ -221,76 +336,23 @@ __global__ void __launch_bounds__(128) ZK_ACCUM_G1_ATTR k_msm_accum(SegBases<typ
     q.next(key, ent, start, e, g, en);
     if (g != cur) {
       const bool head = (run_start == start) && (off[cur] < start);
-      if (head) st_vec(&partials[2 * (size_t)t], acc);
-      else st_vec(&buckets[cur], acc);
+      if (head) L::st(&partials[2 * (size_t)t], acc);
+      else L::st(&buckets[cur], acc);
       xyzz_set_inf(acc);
       cur = g;
       run_start = e;
     }
     if (en == MSM_DUMMY) continue;   // zero digit (shared-bucket plans)
     // batch: bucket g >> segshift names the MSM whose bases entry en indexes
-    typename C::A a = ld_vec(seg_base(sb, g >> segshift, en & 0x7fffffffu));
+    typename L::B a = L::ld_aff(seg_base(sb, g >> segshift, en & 0x7fffffffu));
     if (en & 0x80000000u) a.y = f_neg(a.y);
     if (!aff_is_inf(a)) acc = xyzz_madd(acc, a);
   }
   const bool head = (run_start == start) && (off[cur] < start);
   const bool tail = off[cur + 1] > end;
-  if (head) st_vec(&partials[2 * (size_t)t], acc);
-  else if (tail) st_vec(&partials[2 * (size_t)t + 1], acc);
-  else st_vec(&buckets[cur], acc);
-}
-
-// G2 accumulate over lane pairs (Fq2h, ff.hpp): chunk t is owned by lanes
-// 2t, 2t+1, each holding one Fq coefficient of every Fq2 coordinate.  The
-// loop, its branches and the flushes are those of k_msm_accum; the pair's
-// two lanes read and write the two 48-byte halves of each point.
-ZK_DI void st_pair(G2X* p, const XYZZ<Fq2h>& a) {
-  Fq* q = reinterpret_cast<Fq*>(p) + pair_half();
-  st_vec(q + 0, a.X.v);
-  st_vec(q + 2, a.Y.v);
-  st_vec(q + 4, a.ZZ.v);
-  st_vec(q + 6, a.ZZZ.v);
-}
-__global__ void __launch_bounds__(128) ZK_ACCUM_G2_ATTR k_msm_accum_pair(SegBases<G2A> sb, uint32_t segshift,
-                                                                      const uint32_t* __restrict__ ent,
-                                                                      const uint32_t* __restrict__ key,
-                                                                      const uint32_t* __restrict__ off, uint32_t G,
-                                                                      uint32_t T, G2X* __restrict__ buckets,
-                                                                      G2X* __restrict__ partials) {
-  const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;
-  const uint32_t h = pair_half();
-  const uint32_t M = off[G];
-  const uint32_t K = chunk_len(M, T);
-  const uint32_t start = t * K;
-  if (t >= T || start >= M) return;   // uniform over the pair
-  const uint32_t end = min(start + K, M);
-  XYZZ<Fq2h> acc;
-  xyzz_set_inf(acc);
-  uint32_t cur = key[start], run_start = start;
-  __shared__ uint32_t entq_lds[2 * ENTQ_LDS_WORDS];   // 128 threads = 2 waves
-  EntQ q(entq_lds);
-  for (uint32_t e = start; e < end; e++) {
-    uint32_t g, en;
-    q.next(key, ent, start, e, g, en);
-    if (g != cur) {
-      const bool head = (run_start == start) && (off[cur] < start);
-      if (head) st_pair(&partials[2 * (size_t)t], acc);
-      else st_pair(&buckets[cur], acc);
-      xyzz_set_inf(acc);
-      cur = g;
-      run_start = e;
-    }
-    if (en == MSM_DUMMY) continue;
-    const Fq* bp = reinterpret_cast<const Fq*>(seg_base(sb, g >> segshift, en & 0x7fffffffu)) + h;
-    Affine<Fq2h> a{{ld_vec(bp)}, {ld_vec(bp + 2)}};
-    if (en & 0x80000000u) a.y = f_neg(a.y);
-    if (!aff_is_inf(a)) acc = xyzz_madd(acc, a);
-  }
-  const bool head = (run_start == start) && (off[cur] < start);
-  const bool tail = off[cur + 1] > end;
-  if (head) st_pair(&partials[2 * (size_t)t], acc);
-  else if (tail) st_pair(&partials[2 * (size_t)t + 1], acc);
-  else st_pair(&buckets[cur], acc);
+  if (head) L::st(&partials[2 * (size_t)t], acc);
+  else if (tail) L::st(&partials[2 * (size_t)t + 1], acc);
+  else L::st(&buckets[cur], acc);
 }
 
 // Buckets whose entries span several accumulate chunks.  A bucket over
@@ -317,51 +379,33 @@ __global__ void __launch_bounds__(128) ZK_ACCUM_G2_ATTR k_msm_accum_pair(SegBase
 #endif
 constexpr int MSM_MERGE_FAN = 1 << ZK_MERGE_FAN_LOG;
 
-// The latency-bound G1 reductions (fixup, row/column sums, quantities, the
-// tree merge) run their adds without the scheduling barriers
-// (xyzz_add_ilp), so independent products overlap; ZK_TAIL_ILP=0 (build
-// flag) restores them (A/B).  The one-lane G2 path keeps them (its 96-VGPR
-// points would spill).
-#ifndef ZK_TAIL_ILP
-#define ZK_TAIL_ILP 1
-#endif
+// The latency-bound reductions (fixup, combine, row/column sums, the G1 tree
+// merge) run their adds without the scheduling barriers (xyzz_add_ilp), so
+// independent products overlap.  The G2 merge adds full Fq2
+// points on one lane and keeps the barriers (its 96-VGPR points would spill).
 template <class F>
 ZK_DI XYZZ<F> tail_add(const XYZZ<F>& p, const XYZZ<F>& q) {
-  return xyzz_add(p, q);
+  return xyzz_add_ilp(p, q);
 }
-ZK_DI XYZZ<Fq> tail_add(const XYZZ<Fq>& p, const XYZZ<Fq>& q) {
-  if constexpr (ZK_TAIL_ILP != 0) return xyzz_add_ilp(p, q);
-  else return xyzz_add(p, q);
-}
-// G2 lane-pair sums (row/column sums, fixup) as well: prove 9.61 -> 9.55 ms
-// (median of 5 alternating pairs, profiles/r02_ab_g2_ilp.txt; the 408 B of
-// scratch are the out-of-line doubling call, with or without); ZK_TAIL_ILP_G2=0
-// (build flag) keeps their barriers
-
-#ifndef ZK_TAIL_ILP_G2
-#define ZK_TAIL_ILP_G2 1
-#endif
-ZK_DI XYZZ<Fq2h> tail_add(const XYZZ<Fq2h>& p, const XYZZ<Fq2h>& q) {
-  if constexpr (ZK_TAIL_ILP_G2 != 0) return xyzz_add_ilp(p, q);
-  else return xyzz_add(p, q);
-}
+ZK_DI XYZZ<Fq2> tail_add(const XYZZ<Fq2>& p, const XYZZ<Fq2>& q) { return xyzz_add(p, q); }
 
 __device__ __forceinline__ bool big_bucket(const uint32_t* off, uint32_t b, uint32_t K, uint32_t fix_max) {
   return (off[b + 1] - 1) / K - off[b] / K + 1 > fix_max;
 }
 
-// One thread per bucket, or -- when there are more buckets than chunks
-// (by_boundary: the 2^19-bucket full-width MSM, where most buckets lie inside
-// one chunk and most per-bucket lanes would idle) one thread per chunk
-// boundary u, which takes the bucket holding entry u K if u is the first
-// boundary inside it.
+// One unit per bucket, or -- when there are more buckets than chunks
+// (by_boundary: the 2^19-bucket full-width MSM, or c = 22 at 2^24 with 2^21
+// buckets over 65 K chunks, where most buckets lie inside one chunk and most
+// per-bucket units would idle; one lane pair per bucket cost G2 1.15 ms per
+// 2^24 proof) one unit per chunk boundary u, which takes the bucket holding
+// entry u K if u is the first boundary inside it.
 template <class C>
 __global__ void __launch_bounds__(128) k_msm_fixup(const uint32_t* __restrict__ key, const uint32_t* __restrict__ off,
                                                    uint32_t G, uint32_t T, uint32_t fix_max, bool by_boundary,
                                                    uint32_t* __restrict__ nbig, typename C::X* __restrict__ buckets,
                                                    const typename C::X* __restrict__ partials) {
-  using X = typename C::X;
-  const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+  using L = Lanes<C>;
+  const uint32_t u = (blockIdx.x * blockDim.x + threadIdx.x) / L::N;   // uniform over the unit from here on
   const uint32_t K = chunk_len(off[G], T);
   uint32_t g = u;
   if (by_boundary) {
@@ -376,23 +420,13 @@ __global__ void __launch_bounds__(128) k_msm_fixup(const uint32_t* __restrict__ 
   const uint32_t t0 = bs / K, t1 = (be - 1) / K;
   if (t0 == t1) return;
   if (t1 - t0 + 1 > fix_max) {   // left to the merge levels, which skip themselves when none exist
-    atomicAdd(nbig, 1u);
+    if (L::lead()) atomicAdd(nbig, 1u);   // once per bucket
     return;
   }
-  X acc = ld_vec(&partials[2 * (size_t)t0 + 1]);
-  for (uint32_t t = t0 + 1; t <= t1; t++) acc = tail_add(acc, ld_vec(&partials[2 * (size_t)t]));
-  st_vec(&buckets[g], acc);
-}
-
-template <class X>
-__device__ __forceinline__ X shfl_xor_point(const X& v, int d) {
-  constexpr int NW = sizeof(X) / 4;
-  X o;
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(&v);
-  uint32_t* dst = reinterpret_cast<uint32_t*>(&o);
-#pragma unroll
-  for (int k = 0; k < NW; k++) dst[k] = __shfl_xor(src[k], d);
-  return o;
+  typename L::P acc = L::ld(&partials[2 * (size_t)t0 + 1]);
+#pragma unroll 1
+  for (uint32_t t = t0 + 1; t <= t1; t++) acc = tail_add(acc, L::ld(&partials[2 * (size_t)t]));
+  L::st(&buckets[g], acc);
 }
 
 // All merge levels in ONE launch (round 5; was one launch per level, 8-9
@@ -472,12 +506,13 @@ __global__ void __launch_bounds__(128) k_msm_merge(const uint32_t* __restrict__ 
 }
 
 // ------------------------------------------------------------- reduce ---
-// One wave64 per sum: lane l folds terms l, l+64, ... serially (all lanes
-// busy), then a 6-step butterfly over __shfl_xor (no LDS, so occupancy is
-// set by VGPRs alone; a G2 point is 96 dwords -- 96 cross-lane moves per
-// step against ~20K instructions per add).  Both phases run through ONE
-// xyzz_add call site: the loop is not unrolled, so the kernel's code stays
-// a single add (I-cache) instead of 1 + 6 inlined copies.
+// Row/column sums, one wave64 per sum: unit u of the wave (64 / N units,
+// Lanes<C>) folds terms u, u + 64 / N, ... serially (all lanes busy); for G1
+// one more single-lane step adds the sums of lanes l and l + 32; the wave
+// tail then sums the 32 unit points left with 4-lane adds over __shfl_xor
+// (no LDS, so occupancy is set by VGPRs alone).  The serial phase and the
+// xor-32 step run through ONE tail_add call site: the loop is not unrolled,
+// so the kernel's code stays a single add (I-cache) instead of inlined copies.
 
 constexpr int MSM_RED_WAVES = 4;   // sums per 256-thread workgroup
 
@@ -526,324 +561,123 @@ ZK_DI uint32_t quant_term(const QuantSpan& s, uint32_t k) {
   return ((k >> bb) << (bb + 1)) | (1u << bb) | (k & ((1u << bb) - 1));
 }
 
-template <class X>
-__device__ __forceinline__ X shfl_point(const X& v, int src) {
-  constexpr int NW = sizeof(X) / 4;
-  X o;
-  const uint32_t* s = reinterpret_cast<const uint32_t*>(&v);
-  uint32_t* d = reinterpret_cast<uint32_t*>(&o);
-#pragma unroll
-  for (int k = 0; k < NW; k++) d[k] = __shfl(s[k], src);
-  return o;
-}
-
-// The wave's 64 lane points summed by lane-quad adds (curve.hpp): the 32
-// sums of lanes l and l + 32 (the caller's last single-lane step) are folded
-// in 5 quad rounds -- 16 adds (quad j: lanes 2j, 2j + 1), then 8, 4, 2, 1 --
-// instead of 5 more single-lane butterfly steps; a quad add issues about a
-// third of a single-lane add's instructions, and these steps are the
-// latency-bound tail of every sum.  The total is in lanes 0-3.
-#ifndef ZK_ROWCOL_QTAIL
-#define ZK_ROWCOL_QTAIL 1
-#endif
-template <class X>
-ZK_DI X wave_tail_quad(const X& v) {
-  const int j = (threadIdx.x & 63) >> 2;
-  X t;
-#pragma unroll 1
-  for (int it = 0; it < 5; it++) {
-    X a, b;
-    if (it == 0) {
-      a = shfl_point(v, 2 * j);
-      b = shfl_point(v, 2 * j + 1);
-    } else {
-      a = t;
-      b = shfl_xor_point(t, 64 >> it);
-    }
-    t = xyzz_add_quad(a, b);
-  }
-  return t;
-}
-
 // Row sums C_hi (2^kc contiguous buckets) and column sums D_lo (2^kr buckets
 // at stride 2^kc) of every window, one wave each.
 template <class C>
 __global__ void __launch_bounds__(64 * MSM_RED_WAVES) k_msm_rowcol(MsmPlan p, const uint32_t* __restrict__ off,
                                                                   const typename C::X* __restrict__ buckets,
                                                                   typename C::X* __restrict__ rc) {
-  using X = typename C::X;
+  using L = Lanes<C>;
+  using P = typename L::P;
+  constexpr uint32_t UW = 64 / L::N;   // units per wave
   const uint32_t b = blockIdx.x * MSM_RED_WAVES + (threadIdx.x >> 6);
-  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t unit = (threadIdx.x & 63) / L::N;
   if (b >= p.nrc) return;   // whole waves
   const SumSpan sp = rowcol_span(p, b);
   const uint32_t len = sp.len, g0 = sp.g0, stride = sp.stride;
-  const uint32_t niter = (len + 63) >> 6;
-  constexpr uint32_t NB = ZK_ROWCOL_QTAIL ? 1 : 6;   // single-lane butterfly steps
-  X v;
+  const uint32_t niter = (len + UW - 1) / UW;
+  P v;
   xyzz_set_inf(v);
 #pragma unroll 1
-  for (uint32_t it = 0; it < niter + NB; it++) {
-    X o;
+  for (uint32_t it = 0; it < niter + L::XOR32; it++) {
+    P o;
     if (it < niter) {
-      const uint32_t t = it * 64 + lane, g = g0 + t * stride;
-      if (t < len && (p.all_valid || off[g + 1] != off[g])) o = ld_vec(&buckets[g]);
+      const uint32_t t = it * UW + unit, g = g0 + t * stride;
+      if (t < len && (p.all_valid || off[g + 1] != off[g])) o = L::ld(&buckets[g]);
       else xyzz_set_inf(o);
     } else {
-      o = shfl_xor_point(v, ZK_ROWCOL_QTAIL ? 32 : 1 << (it - niter));
+      o = shfl_point<true>(v, 32);
     }
     v = tail_add(v, o);
   }
-  if constexpr (ZK_ROWCOL_QTAIL) v = wave_tail_quad(v);
-  if (lane == 0) st_vec(&rc[b], v);
+  v = L::wave_tail(v);
+  if ((threadIdx.x & 63) < L::N) L::st(&rc[b], v);
 }
 
-// ---- lane-quad reductions (xyzz_add_quad) ------------------------------
-// The same sums with each add split over the 4 lanes of a quad (curve.hpp):
-// one sum per workgroup of RW waves = 16 RW quads.  Quad j folds terms j,
+// Quantities: one sum per workgroup of RW waves = 16 RW groups of 4 lanes,
+// every add split over the group (Lanes<C>::add4).  Group j folds terms j,
 // j + 16 RW, ... serially, a 4-step __shfl_xor butterfly (lane distances
-// 4..32 keep each lane's quad position) combines a wave, then a log2(RW)-step
-// tree over LDS combines the waves (wave w + 2^k hands its total to wave w
-// in step k).  One xyzz_add_quad call site.  The G1 quantities (tens of
-// sums) run on quads, ZK_QUANT_WAVES_G1 waves per sum (4: one wave per SIMD,
-// 2 terms per quad before the butterfly; round 5: prove 9.173 vs 9.252 ms
-// with 8, median of 4 alternating processes, profiles/r05_ab_quant_waves.txt);
-// the G2 ones on lane pairs (k_msm_quant_pair).
+// 4..32 keep each lane's place in its group) combines a wave, then a
+// log2(RW)-step tree over LDS combines the waves (wave w + 2^k hands its
+// total to wave w in step k).  One add4 call site.  ZK_QUANT_WAVES_G1 /
+// ZK_QUANT_WAVES_G2 waves per sum (G1 4: one wave per SIMD, 2 terms per quad
+// before the butterfly; round 5: prove 9.173 vs 9.252 ms with 8, median of 4
+// alternating processes, profiles/r05_ab_quant_waves.txt).  A lane-quad add
+// on the full Fq2 point spills (792 B per lane) at one wave per SIMD, hence
+// the G2 duos.
 #ifndef ZK_QUANT_WAVES_G1
 #define ZK_QUANT_WAVES_G1 4
+#endif
+#ifndef ZK_QUANT_WAVES_G2
+#define ZK_QUANT_WAVES_G2 4
 #endif
 
 constexpr int ilog2_c(int x) { return x <= 1 ? 0 : 1 + ilog2_c(x / 2); }
 
-template <class X, int RW>
-__device__ __forceinline__ X quad_sum_step(X v, uint32_t it, uint32_t niter, X* xs, bool have, const X& term) {
-  X o;
+// The operand of step `it`: the group's term (at *tp, if it has one), the
+// butterfly partner's sum, or the sum parked by the wave 2^k further on.
+// Lanes<C>::TERM_AHEAD: the caller has loaded the term already.  Where the
+// load stands decides the register allocation, differently for the two
+// adds: loaded here, the G1 kernel takes 166 VGPRs (3 waves per SIMD)
+// instead of 192; loaded ahead, the G2 kernel takes 232 instead of 209.  Each
+// keeps the form it was measured with (no higher occupancy is assumed
+// better: these kernels share their SIMDs with other streams' kernels).
+template <class C, int RW>
+ZK_DI typename Lanes<C>::P quant_step(typename Lanes<C>::P v, uint32_t it, uint32_t niter, typename Lanes<C>::P* xs,
+                                       bool have, const typename Lanes<C>::P& term, const typename C::X* tp) {
+  using L = Lanes<C>;
+  typename L::P o;
   if (it < niter) {
-    if (have) o = term;
+    if (have) o = L::TERM_AHEAD ? term : L::ld(tp);
     else xyzz_set_inf(o);
   } else if (it < niter + 4) {
-    o = shfl_xor_point(v, 4 << (it - niter));
+    o = shfl_point<true>(v, 4 << (it - niter));
   } else {
     const uint32_t k = it - niter - 4, wave = threadIdx.x >> 6, m = 1u << k;
     __syncthreads();   // the previous step's reads are done
-    if ((wave & (2 * m - 1)) == m && (threadIdx.x & 63) == 0) xs[wave >> (k + 1)] = v;
+    if ((wave & (2 * m - 1)) == m && (threadIdx.x & 63) < L::PARK)
+      xs[L::PARK * (wave >> (k + 1)) + (threadIdx.x & (L::PARK - 1))] = v;
     __syncthreads();
-    if ((wave & (2 * m - 1)) == 0) o = xs[wave >> (k + 1)];
-    else xyzz_set_inf(o);
+    if ((wave & (2 * m - 1)) == 0)
+      o = xs[L::PARK * (wave >> (k + 1)) + (threadIdx.x & (L::PARK - 1))];
+    else
+      xyzz_set_inf(o);
   }
   return o;
 }
 
 template <class C, int RW>
-__global__ void __launch_bounds__(64 * RW) k_msm_quant_q(MsmPlan p, const typename C::X* __restrict__ rc,
-                                                        typename C::X* __restrict__ res) {
-  using X = typename C::X;
-  __shared__ X xs[RW > 1 ? RW / 2 : 1];
-  constexpr uint32_t NQ = 16 * RW;
+__global__ void __launch_bounds__(64 * RW) k_msm_quant(MsmPlan p, const typename C::X* __restrict__ rc,
+                                                      typename C::X* __restrict__ res) {
+  using L = Lanes<C>;
+  using P = typename L::P;
+  __shared__ P xs[L::PARK * (RW > 1 ? RW / 2 : 1)];   // [slot][parked lane]
+  constexpr uint32_t NU = 16 * RW;
   const uint32_t b = blockIdx.x;
-  if (b >= p.nq) return;
+  if (b >= p.nq) return;   // whole workgroup
   const QuantSpan qs = quant_span(p, b);
-  const X* src = rc + qs.src;
+  const typename C::X* src = rc + qs.src;
   const uint32_t j = threadIdx.x >> 2;
-  const uint32_t niter = (qs.cnt + NQ - 1) / NQ;
-  X v;
+  const uint32_t niter = (qs.cnt + NU - 1) / NU;
+  P v;
   xyzz_set_inf(v);
 #pragma unroll 1
   for (uint32_t it = 0; it < niter + 4 + ilog2_c(RW); it++) {
-    X term;
+    P term;
     bool have = false;
-    if (it < niter) {
-      const uint32_t k = it * NQ + j;
-      have = k < qs.cnt;
-      if (have) term = ld_vec(&src[quant_term(qs, k)]);
-    }
-    const X o = quad_sum_step<X, RW>(v, it, niter, xs, have, term);
-    v = xyzz_add_quad(v, o);
-  }
-  if (threadIdx.x == 0) st_vec(&res[b], v);
-}
-
-// ---- lane-pair G2 reductions (Fq2h) -------------------------------------
-// G2 row/column sums and fixup with each add split over a lane pair: half the
-// registers (two waves per SIMD) and half the multiply chain per add on the
-// few hundred latency-bound sums.  Pair j of a wave folds terms j, j + 32,
-// ...; the butterfly's lane distances 2..32 keep each lane's half.
-ZK_DI XYZZ<Fq2h> ld_pair(const G2X* p) {
-  const Fq* q = reinterpret_cast<const Fq*>(p) + pair_half();
-  return {{ld_vec(q + 0)}, {ld_vec(q + 2)}, {ld_vec(q + 4)}, {ld_vec(q + 6)}};
-}
-
-// G2 reduction tails on lane duos (curve.hpp xyzz_add_duo: two lane pairs
-// per add, half the pair add's dependent products).  ZK_G2_DUO=0: A/B build
-// with the lane-pair butterflies.
-#ifndef ZK_G2_DUO
-#define ZK_G2_DUO 1
-#endif
-template <int K>
-ZK_DI XYZZ<Fq2h> duo_bcast_point(const XYZZ<Fq2h>& v) {
-  return {duo_bcast<K>(v.X), duo_bcast<K>(v.Y), duo_bcast<K>(v.ZZ), duo_bcast<K>(v.ZZZ)};
-}
-// The wave's 32 lane-pair points summed on duos: duo j first adds pairs 2j
-// and 2j + 1 (its own two pairs), then 8, 4, 2, 1 duo adds across lanes
-// 32 .. 4 apart.  The total is in lanes 0-3.
-ZK_DI XYZZ<Fq2h> wave_tail_duo(const XYZZ<Fq2h>& v) {
-  XYZZ<Fq2h> t;
-#pragma unroll 1
-  for (int it = 0; it < 5; it++) {
-    XYZZ<Fq2h> a, b;
-    if (it == 0) {
-      a = duo_bcast_point<0>(v);
-      b = duo_bcast_point<1>(v);
-    } else {
-      a = t;
-      b = shfl_xor_point(t, 64 >> it);
-    }
-    t = xyzz_add_duo(a, b);
-  }
-  return t;
-}
-
-__global__ void __launch_bounds__(64 * MSM_RED_WAVES) k_msm_rowcol_pair(MsmPlan p, const uint32_t* __restrict__ off,
-                                                                       const G2X* __restrict__ buckets,
-                                                                       G2X* __restrict__ rc) {
-  const uint32_t b = blockIdx.x * MSM_RED_WAVES + (threadIdx.x >> 6);
-  const uint32_t pr = (threadIdx.x & 63) >> 1;
-  if (b >= p.nrc) return;   // whole waves
-  const SumSpan sp = rowcol_span(p, b);
-  const uint32_t len = sp.len, g0 = sp.g0, stride = sp.stride;
-  const uint32_t niter = (len + 31) >> 5;
-  constexpr uint32_t NB = ZK_G2_DUO ? 0 : 5;   // lane-pair butterfly steps
-  XYZZ<Fq2h> v;
-  xyzz_set_inf(v);
-#pragma unroll 1
-  for (uint32_t it = 0; it < niter + NB; it++) {
-    XYZZ<Fq2h> o;
-    if (it < niter) {
-      const uint32_t t = it * 32 + pr, g = g0 + t * stride;
-      if (t < len && (p.all_valid || off[g + 1] != off[g])) o = ld_pair(&buckets[g]);
-      else xyzz_set_inf(o);
-    } else {
-      o = shfl_xor_point(v, 2 << (it - niter));
-    }
-    v = tail_add(v, o);
-  }
-  if constexpr (ZK_G2_DUO) v = wave_tail_duo(v);
-  if ((threadIdx.x & 63) < 2) st_pair(&rc[b], v);
-}
-
-// G2 quantities on lane pairs over ZK_QUANT_WAVES_G2 waves: pair j of the
-// workgroup folds terms j, j + 32 RW, ..., a 5-step __shfl_xor butterfly
-// (lane distances 2..32 keep each lane's half) combines a wave, then a
-// log2(RW)-step tree over LDS combines the waves.  Round 5: was the lane-quad
-// kernel on the full Fq2 point, which spills (792 B per lane) at one wave
-// per SIMD.
-#ifndef ZK_QUANT_WAVES_G2
-#define ZK_QUANT_WAVES_G2 4
-#endif
-template <int RW>
-__global__ void __launch_bounds__(64 * RW) k_msm_quant_pair(MsmPlan p, const G2X* __restrict__ rc,
-                                                           G2X* __restrict__ res) {
-  __shared__ XYZZ<Fq2h> xs[RW > 1 ? RW : 2];   // [slot][half]
-  constexpr uint32_t NP = 32 * RW;
-  constexpr uint32_t LR = ilog2_c(RW);
-  const uint32_t b = blockIdx.x;
-  if (b >= p.nq) return;   // whole workgroup
-  const QuantSpan qs = quant_span(p, b);
-  const G2X* src = rc + qs.src;
-  const uint32_t j = threadIdx.x >> 1, wave = threadIdx.x >> 6;
-  const uint32_t niter = (qs.cnt + NP - 1) / NP;
-  XYZZ<Fq2h> v;
-  xyzz_set_inf(v);
-#pragma unroll 1
-  for (uint32_t it = 0; it < niter + 5 + LR; it++) {
-    XYZZ<Fq2h> o;
-    if (it < niter) {
-      const uint32_t k = it * NP + j;
-      if (k < qs.cnt) o = ld_pair(&src[quant_term(qs, k)]);
-      else xyzz_set_inf(o);
-    } else if (it < niter + 5) {
-      o = shfl_xor_point(v, 2 << (it - niter));
-    } else {
-      const uint32_t k = it - niter - 5, m = 1u << k;
-      __syncthreads();   // the previous step's reads are done
-      if ((wave & (2 * m - 1)) == m && (threadIdx.x & 63) < 2) xs[2 * (wave >> (k + 1)) + pair_half()] = v;
-      __syncthreads();
-      if ((wave & (2 * m - 1)) == 0) o = xs[2 * (wave >> (k + 1)) + pair_half()];
-      else xyzz_set_inf(o);
-    }
-    v = tail_add(v, o);
-  }
-  if (threadIdx.x < 2) st_pair(&res[b], v);
-}
-
-// The G2 quantities on lane duos (ZK_G2_DUO): duo j of the workgroup folds
-// terms j, j + 16 RW, ..., a 4-step __shfl_xor butterfly (lane distances
-// 4 .. 32 keep each lane's duo position), then a log2(RW)-step LDS tree.
-template <int RW>
-__global__ void __launch_bounds__(64 * RW) k_msm_quant_duo(MsmPlan p, const G2X* __restrict__ rc,
-                                                          G2X* __restrict__ res) {
-  __shared__ XYZZ<Fq2h> xs[RW > 1 ? 2 * RW : 4];   // [slot][lane of the duo]
-  constexpr uint32_t NU = 16 * RW;
-  constexpr uint32_t LR = ilog2_c(RW);
-  const uint32_t b = blockIdx.x;
-  if (b >= p.nq) return;   // whole workgroup
-  const QuantSpan qs = quant_span(p, b);
-  const G2X* src = rc + qs.src;
-  const uint32_t j = threadIdx.x >> 2, wave = threadIdx.x >> 6;
-  const uint32_t niter = (qs.cnt + NU - 1) / NU;
-  XYZZ<Fq2h> v;
-  xyzz_set_inf(v);
-#pragma unroll 1
-  for (uint32_t it = 0; it < niter + 4 + LR; it++) {
-    XYZZ<Fq2h> o;
+    const typename C::X* tp = src;
     if (it < niter) {
       const uint32_t k = it * NU + j;
-      if (k < qs.cnt) o = ld_pair(&src[quant_term(qs, k)]);
-      else xyzz_set_inf(o);
-    } else if (it < niter + 4) {
-      o = shfl_xor_point(v, 4 << (it - niter));
-    } else {
-      const uint32_t k = it - niter - 4, m = 1u << k;
-      __syncthreads();   // the previous step's reads are done
-      if ((wave & (2 * m - 1)) == m && (threadIdx.x & 63) < 4) xs[4 * (wave >> (k + 1)) + (threadIdx.x & 3)] = v;
-      __syncthreads();
-      if ((wave & (2 * m - 1)) == 0) o = xs[4 * (wave >> (k + 1)) + (threadIdx.x & 3)];
-      else xyzz_set_inf(o);
+      have = k < qs.cnt;
+      if (have) {
+        tp = &src[quant_term(qs, k)];
+        if (L::TERM_AHEAD) term = L::ld(tp);
+      }
     }
-    v = xyzz_add_duo(v, o);
+    const P o = quant_step<C, RW>(v, it, niter, xs, have, term, tp);
+    v = L::add4(v, o);
   }
-  if (threadIdx.x < 2) st_pair(&res[b], v);
-}
-
-// G2 fixup on lane pairs, per bucket or (by_boundary, more buckets than
-// chunks: c = 22 at 2^24, 2^21 buckets over 65 K chunks) per chunk boundary as
-// k_msm_fixup<G1> (round 5; one pair per bucket cost 1.15 ms per 2^24 proof).
-__global__ void __launch_bounds__(128) k_msm_fixup_pair(const uint32_t* __restrict__ key,
-                                                        const uint32_t* __restrict__ off, uint32_t G, uint32_t T,
-                                                        uint32_t fix_max, bool by_boundary,
-                                                        uint32_t* __restrict__ nbig, G2X* __restrict__ buckets,
-                                                        const G2X* __restrict__ partials) {
-  const uint32_t u = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;   // pair-uniform from here on
-  const uint32_t K = chunk_len(off[G], T);
-  uint32_t g = u;
-  if (by_boundary) {
-    if (u == 0 || u >= T || (uint64_t)u * K >= off[G]) return;
-    g = key[u * K];
-    if (off[g] / K != u - 1) return;   // not split here, or not its first boundary
-  } else if (g >= G) {
-    return;
-  }
-  const uint32_t bs = off[g], be = off[g + 1];
-  if (be == bs) return;
-  const uint32_t t0 = bs / K, t1 = (be - 1) / K;
-  if (t0 == t1) return;
-  if (t1 - t0 + 1 > fix_max) {
-    if (!pair_half()) atomicAdd(nbig, 1u);
-    return;
-  }
-  XYZZ<Fq2h> acc = ld_pair(&partials[2 * (size_t)t0 + 1]);
-#pragma unroll 1
-  for (uint32_t t = t0 + 1; t <= t1; t++) acc = tail_add(acc, ld_pair(&partials[2 * (size_t)t]));
-  st_pair(&buckets[g], acc);
+  if (threadIdx.x < L::N) L::st(&res[b], v);
 }
 
 // Two parts of one split MSM (msm_batch_back COMBINE): bucket g = this
@@ -857,84 +691,53 @@ __global__ void __launch_bounds__(128) k_msm_combine(const uint32_t* __restrict_
                                                      const uint32_t* __restrict__ off_prev, bool prev_all, uint32_t G,
                                                      typename C::X* __restrict__ buckets,
                                                      const typename C::X* __restrict__ prev) {
-  using X = typename C::X;
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= G) return;
-  X a, b;
-  if (off[g + 1] != off[g]) a = ld_vec(&buckets[g]);
+  using L = Lanes<C>;
+  const uint32_t g = (blockIdx.x * blockDim.x + threadIdx.x) / L::N;
+  if (g >= G) return;   // uniform over the unit
+  typename L::P a, b;
+  if (off[g + 1] != off[g]) a = L::ld(&buckets[g]);
   else xyzz_set_inf(a);
-  if (prev_all || off_prev[g + 1] != off_prev[g]) b = ld_vec(&prev[g]);
+  if (prev_all || off_prev[g + 1] != off_prev[g]) b = L::ld(&prev[g]);
   else xyzz_set_inf(b);
-  st_vec(&buckets[g], tail_add(a, b));
-}
-__global__ void __launch_bounds__(128) k_msm_combine_pair(const uint32_t* __restrict__ off,
-                                                          const uint32_t* __restrict__ off_prev, bool prev_all,
-                                                          uint32_t G, G2X* __restrict__ buckets,
-                                                          const G2X* __restrict__ prev) {
-  const uint32_t g = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;
-  if (g >= G) return;   // pair-uniform
-  XYZZ<Fq2h> a, b;
-  if (off[g + 1] != off[g]) a = ld_pair(&buckets[g]);
-  else xyzz_set_inf(a);
-  if (prev_all || off_prev[g + 1] != off_prev[g]) b = ld_pair(&prev[g]);
-  else xyzz_set_inf(b);
-  st_pair(&buckets[g], tail_add(a, b));
+  L::st(&buckets[g], tail_add(a, b));
 }
 
 // ------------------------------------------------------------ driver -----
 
-// Accumulate threads: one full-occupancy round of the chip (blocks per CU
-// from the occupancy calculator x CUs x 128; G2 runs two lanes per chunk).
+// Blocks of `kernel` (block_threads each) that the chip holds at once: its
+// occupancy, at most max_per_cu blocks per CU if that is not 0, times the CUs.
+template <class K>
+static uint32_t resident_blocks(K kernel, int block_threads, int max_per_cu = 0) {
+  int dev = 0, cus = 0, per_cu = 0;
+  ZK_HIP(hipGetDevice(&dev));
+  ZK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  ZK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block_threads, 0));
+  if (max_per_cu) per_cu = std::min(per_cu, max_per_cu);
+  return (uint32_t)std::max(0, per_cu * cus);
+}
+
+// Accumulate units: one full-occupancy round of the chip (128-thread blocks
+// of 2 waves, 128 / N chunks each; ZK_ACCUM_G*_WAVES caps the waves per SIMD).
 template <class C>
 static uint32_t accum_threads() {
-  static const uint32_t T = [] {
-    int dev = 0, cus = 0, per_cu = 0;
-    ZK_HIP(hipGetDevice(&dev));
-    ZK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    constexpr bool pair = std::is_same<C, G2>::value;
-    if constexpr (pair)
-      ZK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_msm_accum_pair, 128, 0));
-    else
-      ZK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_msm_accum<C>, 128, 0));
-#ifdef ZK_ACCUM_G1_WAVES
-    if constexpr (!pair) per_cu = std::min(per_cu, ZK_ACCUM_G1_WAVES * 2);   // 128-thread blocks: 2 waves
-#endif
-#ifdef ZK_ACCUM_G2_WAVES
-    if constexpr (pair) per_cu = std::min(per_cu, ZK_ACCUM_G2_WAVES * 2);
-#endif
-    return (uint32_t)std::max(1, per_cu * cus * (pair ? 64 : 128));
-  }();
+  static const uint32_t T = std::max(
+      1u, resident_blocks(k_msm_accum<C>, 128, 2 * Lanes<C>::ACCUM_WAVES) * (128 / Lanes<C>::N));
   return T;
 }
 
-// Blocks of the merge kernel the chip holds at once (its occupancy x CUs):
-// the upper bound of its grid-barrier launch.
+// Blocks of the merge kernel the chip holds at once: the upper bound of its
+// grid-barrier launch.
 template <class C>
 static uint32_t merge_max_blocks() {
-  static const uint32_t B = [] {
-    int dev = 0, cus = 0, per_cu = 0;
-    ZK_HIP(hipGetDevice(&dev));
-    ZK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    ZK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_msm_merge<C>, 128, 0));
-    return (uint32_t)std::max(0, per_cu * cus);
-  }();
+  static const uint32_t B = resident_blocks(k_msm_merge<C>, 128);
   return B;
 }
 
-// Waves of one row/column-sum launch that the chip holds at once (the
-// kernel's occupancy x CUs), for msm_split_sums.
+// Waves of one row/column-sum launch that the chip holds at once, for
+// msm_split_sums.
 template <class C>
 static uint32_t rowcol_waves() {
-  static const uint32_t W = [] {
-    int dev = 0, cus = 0, per_cu = 0;
-    ZK_HIP(hipGetDevice(&dev));
-    ZK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if constexpr (std::is_same<C, G2>::value)
-      ZK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_msm_rowcol_pair, 64 * MSM_RED_WAVES, 0));
-    else
-      ZK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_msm_rowcol<C>, 64 * MSM_RED_WAVES, 0));
-    return (uint32_t)std::max(1, per_cu * cus * MSM_RED_WAVES);
-  }();
+  static const uint32_t W = std::max(1u, resident_blocks(k_msm_rowcol<C>, 64 * MSM_RED_WAVES) * MSM_RED_WAVES);
   return W;
 }
 
@@ -1020,7 +823,7 @@ static void msm_front_impl(MsmWork& w, const MsmSeg* segs, int nseg, int sw, hip
   // split to fill the chip.  Round 5: the H MSM's 512 sums moved from lane
   // quads (4 waves per sum) to this form, bucket sum 0.285 -> 0.246 ms serial
   // (profiles/r05_ab_qtail_slowbox.txt)
-  if (g2 ? ZK_SPLIT_G2 : ZK_SPLIT_G1) msm_split_sums(p, rowcol_waves<C>(), g2 ? 32u : 64u);
+  if (g2 ? ZK_SPLIT_G2 : ZK_SPLIT_G1) msm_split_sums(p, rowcol_waves<C>(), 64u / Lanes<C>::N);
   w.partials.ensure(sizeof(X) * 2 * (size_t)p.T);
   w.partials2.ensure(sizeof(X) * ((size_t)p.T / 2 + 2));
   w.rc.ensure(sizeof(X) * p.nrc);
@@ -1042,15 +845,9 @@ static void msm_front_impl(MsmWork& w, const MsmSeg* segs, int nseg, int sw, hip
   // accumulate threads split it evenly there (chunk_len), no host sync.
   if (M) {
     ph = pf ? pf->begin(st, (w.tag + (g2 ? "msm_accum_g2" : "msm_accum_g1")).c_str(), n) : -1;
-    if constexpr (g2)
-      k_msm_accum_pair<<<ceil_div(2 * (size_t)p.T, 128), 128, 0, st>>>(sb, p.segshift, w.ent.as<uint32_t>(),
-                                                                        w.key.as<uint32_t>(), w.off.as<uint32_t>(),
-                                                                        p.G, p.T, w.buckets.as<X>(),
-                                                                        w.partials.as<X>());
-    else
-      k_msm_accum<C><<<ceil_div(p.T, 128), 128, 0, st>>>(sb, p.segshift, w.ent.as<uint32_t>(), w.key.as<uint32_t>(),
-                                                          w.off.as<uint32_t>(), p.G, p.T, w.buckets.as<X>(),
-                                                          w.partials.as<X>());
+    k_msm_accum<C><<<ceil_div(Lanes<C>::N * (size_t)p.T, 128), 128, 0, st>>>(
+        sb, p.segshift, w.ent.as<uint32_t>(), w.key.as<uint32_t>(), w.off.as<uint32_t>(), p.G, p.T, w.buckets.as<X>(),
+        w.partials.as<X>());
     ZK_LAUNCH_CHECK();
     if (pf) pf->end(st, ph);
   }
@@ -1069,14 +866,9 @@ static void msm_back_impl(MsmWork& w, hipStream_t st, int mode, const MsmWork* p
   // the merge, [1] its grid barrier
   const bool by_boundary = p.G > p.T;
   const size_t fix_n = by_boundary ? p.T : p.G;
-  if constexpr (g2)
-    k_msm_fixup_pair<<<ceil_div(2 * fix_n, 128), 128, 0, st>>>(
-        w.key.as<uint32_t>(), w.off.as<uint32_t>(), p.G, p.T, p.fix_max, by_boundary, w.nbig.as<uint32_t>(),
-        reinterpret_cast<G2X*>(w.buckets.p), reinterpret_cast<const G2X*>(w.partials.p));
-  else
-    k_msm_fixup<C><<<ceil_div(fix_n, 128), 128, 0, st>>>(w.key.as<uint32_t>(), w.off.as<uint32_t>(), p.G, p.T,
-                                                          p.fix_max, by_boundary, w.nbig.as<uint32_t>(),
-                                                          w.buckets.as<X>(), w.partials.as<X>());
+  k_msm_fixup<C><<<ceil_div(Lanes<C>::N * fix_n, 128), 128, 0, st>>>(
+      w.key.as<uint32_t>(), w.off.as<uint32_t>(), p.G, p.T, p.fix_max, by_boundary, w.nbig.as<uint32_t>(),
+      w.buckets.as<X>(), w.partials.as<X>());
   ZK_LAUNCH_CHECK();
   {
     // level l merges groups of FAN^l chunks; T chunks at most.  The levels
@@ -1100,36 +892,19 @@ static void msm_back_impl(MsmWork& w, hipStream_t st, int mode, const MsmWork* p
   if (mode == MSM_BACK_COMBINE || mode == MSM_BACK_ACCUM) {
     if (!prev || prev->plan.G != p.G || prev->plan.nseg != p.nseg) throw Error(ZK_ERR_ARG, "msm: combine plans differ");
     const bool prev_all = prev->plan.all_valid != 0;
-    if constexpr (g2)
-      k_msm_combine_pair<<<ceil_div(2 * (size_t)p.G, 128), 128, 0, st>>>(
-          w.off.as<uint32_t>(), prev->off.as<uint32_t>(), prev_all, p.G, reinterpret_cast<G2X*>(w.buckets.p),
-          reinterpret_cast<const G2X*>(prev->buckets.p));
-    else
-      k_msm_combine<C><<<ceil_div(p.G, 128), 128, 0, st>>>(w.off.as<uint32_t>(), prev->off.as<uint32_t>(), prev_all,
-                                                            p.G, w.buckets.as<X>(), prev->buckets.as<X>());
+    k_msm_combine<C><<<ceil_div(Lanes<C>::N * (size_t)p.G, 128), 128, 0, st>>>(
+        w.off.as<uint32_t>(), prev->off.as<uint32_t>(), prev_all, p.G, w.buckets.as<X>(), prev->buckets.as<X>());
     ZK_LAUNCH_CHECK();
     p.all_valid = 1;
   }
   if (pf) pf->end(st, ph);
   if (mode == MSM_BACK_FIXUP || mode == MSM_BACK_ACCUM) return;
   ph = pf ? pf->begin(st, (w.tag + "msm_bucket_sum").c_str(), p.G) : -1;   // row/col sums + quantities
-  if constexpr (g2)
-    k_msm_rowcol_pair<<<ceil_div(p.nrc, MSM_RED_WAVES), 64 * MSM_RED_WAVES, 0, st>>>(
-        p, w.off.as<uint32_t>(), reinterpret_cast<const G2X*>(w.buckets.p), reinterpret_cast<G2X*>(w.rc.p));
-  else
-    k_msm_rowcol<C><<<ceil_div(p.nrc, MSM_RED_WAVES), 64 * MSM_RED_WAVES, 0, st>>>(p, w.off.as<uint32_t>(),
-                                                                                  w.buckets.as<X>(), w.rc.as<X>());
+  k_msm_rowcol<C><<<ceil_div(p.nrc, MSM_RED_WAVES), 64 * MSM_RED_WAVES, 0, st>>>(p, w.off.as<uint32_t>(),
+                                                                                w.buckets.as<X>(), w.rc.as<X>());
   ZK_LAUNCH_CHECK();
-  if constexpr (g2) {
-    if constexpr (ZK_G2_DUO)
-      k_msm_quant_duo<ZK_QUANT_WAVES_G2><<<p.nq, 64 * ZK_QUANT_WAVES_G2, 0, st>>>(
-          p, reinterpret_cast<const G2X*>(w.rc.p), reinterpret_cast<G2X*>(w.res.p));
-    else
-      k_msm_quant_pair<ZK_QUANT_WAVES_G2><<<p.nq, 64 * ZK_QUANT_WAVES_G2, 0, st>>>(
-          p, reinterpret_cast<const G2X*>(w.rc.p), reinterpret_cast<G2X*>(w.res.p));
-  }
-  else
-    k_msm_quant_q<C, ZK_QUANT_WAVES_G1><<<p.nq, 64 * ZK_QUANT_WAVES_G1, 0, st>>>(p, w.rc.as<X>(), w.res.as<X>());
+  constexpr int RW = g2 ? ZK_QUANT_WAVES_G2 : ZK_QUANT_WAVES_G1;
+  k_msm_quant<C, RW><<<p.nq, 64 * RW, 0, st>>>(p, w.rc.as<X>(), w.res.as<X>());
   ZK_LAUNCH_CHECK();
   if (pf) pf->end(st, ph);
 }

@@ -166,10 +166,15 @@ int zk_ctx_set_schedule(zk_ctx *ctx, int schedule);
  *   ZK_OPT_POINT_CHUNK    points per kernel launch and device buffer of the
  *                         point decompression / validation calls (default
  *                         2^20, >= 1)
+ *   ZK_OPT_VERIFY_CHUNK   proofs (products) per kernel launch and device
+ *                         buffer of zk_groth16_verify_many /
+ *                         zk_pairing_products (default 65536: one lane per
+ *                         proof, a full wave on every SIMD; >= 1)
  * (Test hooks -- the virtual-rank prove, the bare exchange, fault injection
  * -- live in a separate library, include/zkp_test.h.) */
 enum { ZK_OPT_QUOTIENT_PATH = 1, ZK_OPT_PROVE_WIN_C = 2, ZK_OPT_EXCHANGE_TIMEOUT_MS = 3,
-       ZK_OPT_DIST_QUOTIENT = 5, ZK_OPT_EXCHANGE_FIRST = 6, ZK_OPT_POINT_CHUNK = 7 };
+       ZK_OPT_DIST_QUOTIENT = 5, ZK_OPT_EXCHANGE_FIRST = 6, ZK_OPT_POINT_CHUNK = 7,
+       ZK_OPT_VERIFY_CHUNK = 8 };
 int zk_ctx_set_option(zk_ctx *ctx, int option, int64_t value);
 
 /* ---------------------------------------------------------------- MSM --- */
@@ -435,6 +440,42 @@ int zk_groth16_verify_batch(const zk_vk *vk, const zk_proof *proofs, const zk_fr
 /* prod_i e(g1[i], g2[i]) == 1 -> *result = 1 (Bls12_381::multi_pairing(..)
  * .is_zero(), core:352).  Points must be canonical and on their curves. */
 int zk_pairing_product_is_one(const zk_g1_affine *g1, const zk_g2_affine *g2, size_t n, int *result);
+
+/* ------------------------------------------------------ verify on the GPU --- */
+/* What a proof (or a pairing product) of a batch call can be. */
+typedef enum {
+  ZK_VERIFY_REJECT = 0,      /* the pairing product is not 1 */
+  ZK_VERIFY_ACCEPT = 1,      /* it is 1 */
+  ZK_VERIFY_MALFORMED = 2    /* a point has a coordinate >= p or is off its curve */
+} zk_verify_status;
+/* n_proofs independent Verifier::verify calls (core:308-355) against one vk on
+ * the GPU, one lane per proof (gfx950 pairing kernel, csrc/pairing.hip);
+ * public_inputs is n_proofs x n_inputs, row k for proof k.  status[k] (a
+ * zk_verify_status) is what zk_groth16_verify gives for proof k alone:
+ * *valid = 1 -> ACCEPT, *valid = 0 -> REJECT, ZK_ERR_ARG for a point of the
+ * proof -> MALFORMED.  Returns ZK_OK whenever every proof got a status,
+ * whatever the statuses are; n_inputs != vk->num_public ->
+ * ZK_ERR_INVALID_WITNESS; a malformed vk point or ic_len < n_inputs + 1 ->
+ * ZK_ERR_ARG; a HIP error -> ZK_ERR_DEVICE; n_proofs == 0 -> ZK_OK.  Every
+ * vk point (alpha, beta, gamma, delta and all ic_len entries of ic_g1) is
+ * validated first -- slightly stricter than zk_groth16_verify, which loads
+ * only the ic_g1 entries whose input is non-zero.  As in the reference and the
+ * host verifier no subgroup check is made (a caller that needs one runs
+ * zk_g1_validate / zk_g2_validate first); for on-curve points outside the
+ * r-torsion the status is unspecified (0 or 1) and the call still returns
+ * normally.  The batch crosses the GPU in chunks of ZK_OPT_VERIFY_CHUNK
+ * proofs.  No reference counterpart at batch level: BatchVerifier gives one
+ * bit for the whole batch. */
+int zk_groth16_verify_many(zk_ctx *ctx, const zk_vk *vk, const zk_proof *proofs,
+                           const zk_fr *public_inputs, size_t n_inputs, size_t n_proofs,
+                           uint8_t *status);
+/* n_products pairing products on the GPU, one lane per product: product j =
+ * prod_{i<k} e(g1[jk+i], g2[jk+i]) with k = pairs_per_product; status[j] as
+ * above (ACCEPT: the product is 1 -- zk_pairing_product_is_one's *result = 1;
+ * MALFORMED where that call returns ZK_ERR_ARG).  An infinite point on either
+ * side of a pair contributes 1. */
+int zk_pairing_products(zk_ctx *ctx, const zk_g1_affine *g1, const zk_g2_affine *g2,
+                        size_t pairs_per_product, size_t n_products, uint8_t *status);
 
 #ifdef __cplusplus
 }

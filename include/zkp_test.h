@@ -54,6 +54,21 @@ int zk_test_fq_sqrt(zk_ctx *ctx, const uint64_t *in, size_t n, uint64_t *out, ui
 /* Same in Fq2: 12 words per element (c0 then c1); largest looks at c1, or at
  * c0 when c1 == 0. */
 int zk_test_fq2_sqrt(zk_ctx *ctx, const uint64_t *in, size_t n, uint64_t *out, uint8_t *ok, uint8_t *largest);
+/* The device Fq12 tower behind the pairing kernels (csrc/pairing.hpp), one
+ * lane per element.  An Fq12 crosses as 72 canonical words in tower order
+ * (c0.c0.c0, c0.c0.c1, c0.c1.c0, ...).  out[i] = op(a[i]) or op(a[i], b[i]);
+ * b is read by MUL and LINE_MUL only (else it may be NULL).  LINE_MUL takes
+ * b's c0.c0, c0.c1 and c1.c1 as the three coefficients of a line (its other
+ * coefficients are ignored); CYC_SQR expects a in the cyclotomic subgroup;
+ * FINAL_EXP is a^(3 (p^12 - 1) / r) (the documented c = 3). */
+enum { ZK_TEST_FQ12_MUL = 0, ZK_TEST_FQ12_SQR = 1, ZK_TEST_FQ12_INV = 2, ZK_TEST_FQ12_CONJ = 3,
+       ZK_TEST_FQ12_FROB1 = 4, ZK_TEST_FQ12_FROB2 = 5, ZK_TEST_FQ12_CYC_SQR = 6,
+       ZK_TEST_FQ12_LINE_MUL = 7, ZK_TEST_FQ12_FINAL_EXP = 8 };
+int zk_test_fq12(zk_ctx *ctx, int op, const uint64_t *a, const uint64_t *b, size_t n, uint64_t *out);
+/* The device's final-exponentiated e(g1[i], g2[i]) (on-the-fly Miller loop,
+ * then FINAL_EXP) as n Fq12 of 72 words.  Points must be canonical and on
+ * their curves; an infinite point gives 1. */
+int zk_test_pairing_gt(zk_ctx *ctx, const zk_g1_affine *g1, const zk_g2_affine *g2, size_t n, uint64_t *out);
 
 #ifdef __cplusplus
 }

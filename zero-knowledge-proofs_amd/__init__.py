@@ -55,13 +55,23 @@ EXPORTS = (
     "zk_ctx_detach_exchange",
     "zk_g1_compress", "zk_g2_compress", "zk_g1_decompress", "zk_g2_decompress",
     "zk_g1_validate", "zk_g2_validate",
+    "zk_groth16_verify_many", "zk_pairing_products",
 )
 # include/zkp_test.h (libzkp_amd_test.so)
 TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fault_after_exchange",
-                "zk_test_pk_bases", "zk_test_pk_info", "zk_test_fq_sqrt", "zk_test_fq2_sqrt")
+                "zk_test_pk_bases", "zk_test_pk_info", "zk_test_fq_sqrt", "zk_test_fq2_sqrt",
+                "zk_test_fq12", "zk_test_pairing_gt")
 ZK_OPT_QUOTIENT_PATH, ZK_OPT_PROVE_WIN_C, ZK_OPT_EXCHANGE_TIMEOUT_MS, ZK_OPT_DIST_QUOTIENT = 1, 2, 3, 5
 ZK_OPT_EXCHANGE_FIRST = 6
 ZK_OPT_POINT_CHUNK = 7
+ZK_OPT_VERIFY_CHUNK = 8
+# zk_verify_status: what a proof / pairing product of a GPU batch call can be
+ZK_VERIFY_REJECT, ZK_VERIFY_ACCEPT, ZK_VERIFY_MALFORMED = range(3)
+# ops of zk_test_fq12 (include/zkp_test.h); FINAL_EXP computes a^(FINAL_EXP_C (p^12 - 1) / r)
+(ZK_TEST_FQ12_MUL, ZK_TEST_FQ12_SQR, ZK_TEST_FQ12_INV, ZK_TEST_FQ12_CONJ, ZK_TEST_FQ12_FROB1, ZK_TEST_FQ12_FROB2,
+ ZK_TEST_FQ12_CYC_SQR, ZK_TEST_FQ12_LINE_MUL, ZK_TEST_FQ12_FINAL_EXP) = range(9)
+FINAL_EXP_C = 3
+FQ12_WORDS = 72
 # zk_point_status: what a decompressed / validated point can be
 ZK_POINT_OK, ZK_POINT_ENCODING, ZK_POINT_NOT_CANONICAL, ZK_POINT_NOT_ON_CURVE, ZK_POINT_NOT_IN_SUBGROUP = range(5)
 POINT_STATUS_TEXT = ("valid", "bad encoding flags", "coordinate not below p", "not on the curve",
@@ -395,9 +405,11 @@ class Context:
         afterwards), ZK_OPT_EXCHANGE_TIMEOUT_MS (>= 1), ZK_OPT_DIST_QUOTIENT
         (-1 distributed when an exchange of the key's shape is attached, 0
         replicated), ZK_OPT_EXCHANGE_FIRST (0 MSMs start with the witness, 1
-        they wait for the distributed quotient) or ZK_OPT_POINT_CHUNK (points
-        per launch of the decompress / validate calls, >= 1).  Explicit path
-        choices for tests and A/B runs."""
+        they wait for the distributed quotient), ZK_OPT_POINT_CHUNK (points
+        per launch of the decompress / validate calls, >= 1) or
+        ZK_OPT_VERIFY_CHUNK (proofs / products per launch of verify_many /
+        pairing_products, default 65536, >= 1).  Explicit path choices for
+        tests and A/B runs."""
         _check(lib().zk_ctx_set_option(C.c_void_p(self._h), C.c_int(int(option)), C.c_int64(int(value))), self,
                "zk_ctx_set_option")
 
@@ -501,6 +513,77 @@ class Context:
     def g2_validate(self, arr):
         """zk_g2_validate: (n, 25) affine words -> n statuses."""
         return self._validate("zk_g2_validate", arr, G2_WORDS)
+
+    # ---- batch verification on the GPU (one lane per proof / product) ----
+    def verify_many(self, vk, proofs, inputs):
+        """zk_groth16_verify_many: n proofs (Proof objects, or an (n, 51)
+        uint64 array of their words) against one vk, inputs an (n, n_inputs,
+        4) uint64 array or n rows of ints -> n uint8 ZK_VERIFY_* statuses,
+        each what Verifier.verify says for that proof alone (MALFORMED where
+        it raises ValueError).  InvalidWitness when n_inputs != vk.num_public."""
+        if isinstance(proofs, np.ndarray):
+            pw = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 2 * G1_WORDS + G2_WORDS)
+        else:
+            pw = np.ascontiguousarray([p.words for p in proofs], dtype=np.uint64).reshape(-1, 2 * G1_WORDS + G2_WORDS)
+        n = len(pw)
+        if isinstance(inputs, np.ndarray) and inputs.ndim == 3:
+            inp = np.ascontiguousarray(inputs, dtype=np.uint64)
+        else:
+            rows = [_fr_rows(r) for r in inputs]
+            if len({len(r) for r in rows}) > 1:
+                raise InvalidWitness("verify_many: rows of public inputs of different lengths")
+            inp = np.zeros((len(rows), len(rows[0]) if rows else vk.num_public, 4), dtype=np.uint64)
+            for k, r in enumerate(rows):
+                inp[k] = r
+        if len(inp) != n or inp.shape[2] != 4:
+            raise ValueError("verify_many: one row of public inputs (n_inputs x 4 words) per proof")
+        st = np.zeros(n, dtype=np.uint8)
+        rc = lib().zk_groth16_verify_many(C.c_void_p(self._h), C.byref(vk.s), _p(pw) if n else None,
+                                          _p(inp) if inp.size else None, C.c_size_t(inp.shape[1]), C.c_size_t(n),
+                                          _p(st) if n else None)
+        _check(rc, self, "zk_groth16_verify_many")
+        return st
+
+    def pairing_products(self, g1_points, g2_points, pairs_per_product):
+        """zk_pairing_products: product j = prod_{i<k} e(g1[jk+i], g2[jk+i])
+        with k = pairs_per_product -> one uint8 ZK_VERIFY_* status per product
+        (ACCEPT: the product is 1; MALFORMED: a point of it is not canonical
+        or off its curve)."""
+        a = np.ascontiguousarray(g1_points, dtype=np.uint64).reshape(-1, G1_WORDS)
+        b = np.ascontiguousarray(g2_points, dtype=np.uint64).reshape(-1, G2_WORDS)
+        k = int(pairs_per_product)
+        if len(a) != len(b) or k < 1 or len(a) % k:
+            raise ValueError("as many G1 as G2 points, a whole number of products")
+        n = len(a) // k
+        st = np.zeros(n, dtype=np.uint8)
+        rc = lib().zk_pairing_products(C.c_void_p(self._h), _p(a) if n else None, _p(b) if n else None, C.c_size_t(k),
+                                       C.c_size_t(n), _p(st) if n else None)
+        _check(rc, self, "zk_pairing_products")
+        return st
+
+    # ---- the pairing's test hooks (include/zkp_test.h) ----
+    def test_fq12(self, op, a, b=None):
+        """zk_test_fq12: (n, 72) canonical words -> (n, 72)."""
+        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, FQ12_WORDS)
+        out = np.zeros_like(a)
+        if b is not None:
+            b = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, FQ12_WORDS)
+            if len(b) != len(a):
+                raise ValueError("as many b as a")
+        _check(test_lib().zk_test_fq12(C.c_void_p(self._h), C.c_int(int(op)), _p(a), _p(b) if b is not None else None,
+                                       C.c_size_t(len(a)), _p(out)), self, "zk_test_fq12")
+        return out
+
+    def test_pairing_gt(self, g1_points, g2_points):
+        """zk_test_pairing_gt: the device's final-exponentiated e(P_i, Q_i), (n, 72) words."""
+        a = np.ascontiguousarray(g1_points, dtype=np.uint64).reshape(-1, G1_WORDS)
+        b = np.ascontiguousarray(g2_points, dtype=np.uint64).reshape(-1, G2_WORDS)
+        if len(a) != len(b):
+            raise ValueError("as many G1 as G2 points")
+        out = np.zeros((len(a), FQ12_WORDS), dtype=np.uint64)
+        _check(test_lib().zk_test_pairing_gt(C.c_void_p(self._h), _p(a), _p(b), C.c_size_t(len(a)), _p(out)), self,
+               "zk_test_pairing_gt")
+        return out
 
     # ---- NTT (ark-poly Radix2EvaluationDomain fft / ifft / coset) ----
     def ntt(self, data, inverse=False, coset=None):
@@ -1216,6 +1299,25 @@ class Verifier:
                                      C.c_size_t(len(inp)), C.byref(valid))
         _check(rc, None, "zk_groth16_verify")
         return bool(valid.value)
+
+    @staticmethod
+    def verify_many(vk, proofs_and_inputs, ctx=None):
+        """n independent verify() calls against one vk on the GPU
+        (Context.verify_many) -> bool array, entry k what verify(vk,
+        *proofs_and_inputs[k]) returns.  ValueError naming the first
+        malformed proof, InvalidWitness on an input-count mismatch."""
+        ctx = ctx or default_context()
+        rows = [_fr_rows(inp) for _, inp in proofs_and_inputs]
+        if any(len(r) != vk.num_public for r in rows):
+            raise InvalidWitness("verify_many: a proof's public inputs do not match vk.num_public")
+        inp = np.zeros((len(rows), vk.num_public, 4), dtype=np.uint64)
+        for k, r in enumerate(rows):
+            inp[k] = r
+        st = ctx.verify_many(vk, [p for p, _ in proofs_and_inputs], inp)
+        bad = np.flatnonzero(st == ZK_VERIFY_MALFORMED)
+        if len(bad):
+            raise ValueError(f"verify_many: proof {int(bad[0])} has a point that is not canonical or not on its curve")
+        return st == ZK_VERIFY_ACCEPT
 
 
 class BatchVerifier:

@@ -66,6 +66,7 @@ struct zk_ctx {
                                                // is attached, 0 never (each rank the whole quotient)
   int exchange_first = 0;                      // 1: distributed proofs run the quotient before the MSMs
   size_t point_chunk = (size_t)1 << 20;        // points per launch of the decompress / validate calls
+  size_t verify_chunk = (size_t)1 << 16;       // proofs / products per launch of the batch verification calls
 
   zk::NttDomain& domain(uint32_t log_n);
 };

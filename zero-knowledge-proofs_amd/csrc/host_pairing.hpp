@@ -18,6 +18,7 @@
 #pragma once
 #include <vector>
 
+#include "../../include/zkp.h"
 #include "host_ec.hpp"
 
 namespace zk {
@@ -181,6 +182,38 @@ inline X<F> from_affine(const F& x, const F& y, bool at_inf) {
 // r P == O (ark's Validate::Yes subgroup check)
 inline bool in_subgroup(const A1& p) { return p.inf || is_inf(mul_scalar(from_affine(p.x, p.y, false), FR_MOD64)); }
 inline bool in_subgroup(const A2& p) { return p.inf || is_inf(mul_scalar(from_affine(p.x, p.y, false), FR_MOD64)); }
+
+// ------------------------------------------------------- ABI points -----
+// canonical words -> Montgomery
+inline Fq fq_in(const uint64_t* w) {
+  Fq c;
+  std::memcpy(c.l, w, 48);
+  return to_mont(c);
+}
+
+// ABI point -> host affine; false when a coordinate is not canonical or the
+// point is off the curve (no ark value looks like that)
+inline bool load(const zk_g1_affine& a, A1& p) {
+  p.inf = a.infinity != 0;
+  p.x = zero();
+  p.y = zero();
+  if (p.inf) return true;
+  if (geq_m(a.x) || geq_m(a.y)) return false;
+  p.x = fq_in(a.x);
+  p.y = fq_in(a.y);
+  return on_curve(p);
+}
+inline bool load(const zk_g2_affine& a, A2& p) {
+  p.inf = a.infinity != 0;
+  p.x = fq2_zero();
+  p.y = fq2_zero();
+  if (p.inf) return true;
+  for (int k = 0; k < 2; k++)
+    if (geq_m(a.x + 6 * k) || geq_m(a.y + 6 * k)) return false;
+  p.x = {fq_in(a.x), fq_in(a.x + 6)};
+  p.y = {fq_in(a.y), fq_in(a.y + 6)};
+  return on_curve(p);
+}
 
 }  // namespace host
 }  // namespace zk

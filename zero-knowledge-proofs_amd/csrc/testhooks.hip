@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "pairing.hpp"
 #include "points.hpp"
 #include "../../include/zkp_test.h"
 
@@ -165,6 +166,108 @@ int zk_test_fq_sqrt(zk_ctx* ctx, const uint64_t* in, size_t n, uint64_t* out, ui
 int zk_test_fq2_sqrt(zk_ctx* ctx, const uint64_t* in, size_t n, uint64_t* out, uint8_t* ok, uint8_t* largest) {
   if (!ctx || (n && (!in || !out || !ok || !largest))) return ZK_ERR_ARG;
   ZK_TGUARD(ctx, { return test_sqrt<2>(ctx, in, n, out, ok, largest); })
+}
+
+// ---- the Fq12 tower and the pairing of pairing.hpp on their own -----------
+namespace zk {
+__device__ __forceinline__ void t_read_f12(const uint64_t* w, F12* a) {
+  F2* co = &a->c0.c0;
+#pragma unroll 1
+  for (int j = 0; j < 6; j++) co[j] = {{pt_to_mont(pr_read_fq(w + 12 * j)), pt_to_mont(pr_read_fq(w + 12 * j + 6))}};
+}
+__device__ __forceinline__ void t_write_f12(uint64_t* w, const F12* a) {
+  const F2* co = &a->c0.c0;
+#pragma unroll 1
+  for (int j = 0; j < 6; j++) {
+    pr_write_fq(w + 12 * j, pt_from_mont(co[j].v.c0));
+    pr_write_fq(w + 12 * j + 6, pt_from_mont(co[j].v.c1));
+  }
+}
+__global__ void __launch_bounds__(64) k_test_fq12(int op, const uint64_t* __restrict__ a, const uint64_t* __restrict__ b,
+                                                  size_t n, uint64_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  F12 x, y, r;
+  t_read_f12(a + 72 * i, &x);
+  if (op == ZK_TEST_FQ12_MUL || op == ZK_TEST_FQ12_LINE_MUL) t_read_f12(b + 72 * i, &y);
+  switch (op) {
+    case ZK_TEST_FQ12_MUL: f12_mul(&r, &x, &y); break;
+    case ZK_TEST_FQ12_SQR: f12_sqr(&r, &x); break;
+    case ZK_TEST_FQ12_INV: f12_inv(&r, &x); break;
+    case ZK_TEST_FQ12_CONJ: f12_conj(&r, &x); break;
+    case ZK_TEST_FQ12_FROB1: f12_frob1(&r, &x); break;
+    case ZK_TEST_FQ12_FROB2: f12_frob2(&r, &x); break;
+    case ZK_TEST_FQ12_CYC_SQR: f12_cyc_sqr(&r, &x); break;
+    case ZK_TEST_FQ12_LINE_MUL: {
+      const F2 l[3] = {y.c0.c0, y.c0.c1, y.c1.c1};
+      r = x;
+      f12_mul_line(&r, l);
+      break;
+    }
+    default: r = x; f12_final_exp(&r); break;
+  }
+  t_write_f12(out + 72 * i, &r);
+}
+__global__ void __launch_bounds__(64) k_test_pairing_gt(const uint64_t* __restrict__ g1, const uint64_t* __restrict__ g2,
+                                                        size_t n, uint64_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  PrPairs in;
+  Affine<FqC> P;
+  bool p_inf, q_inf;
+  bool ok = pr_load_g1(g1 + 13 * i, &P, &p_inf);
+  ok = pr_load_g2(g2 + 25 * i, &in.Q, &q_inf) && ok;
+  in.on[0] = ok && !p_inf && !q_inf;
+  in.on[1] = in.on[2] = false;
+  in.xp[0] = P.x.v;
+  in.yp[0] = P.y.v;
+  in.tab[0] = in.tab[1] = nullptr;
+  F12 f;
+  pr_miller(&f, &in);
+  f12_conj(&f, &f);
+  f12_final_exp(&f);
+  t_write_f12(out + 72 * i, &f);
+}
+}  // namespace zk
+
+int zk_test_fq12(zk_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
+  const bool two = op == ZK_TEST_FQ12_MUL || op == ZK_TEST_FQ12_LINE_MUL;
+  if (!ctx || op < ZK_TEST_FQ12_MUL || op > ZK_TEST_FQ12_FINAL_EXP || (n && (!a || !out || (two && !b))))
+    return ZK_ERR_ARG;
+  if (!n) return ZK_OK;
+  ZK_TGUARD(ctx, {
+    DevBuf d_a, d_b, d_out;
+    const size_t bytes = 8 * 72 * n;
+    d_a.ensure(bytes);
+    d_b.ensure(bytes);
+    d_out.ensure(bytes);
+    hipStream_t st = ctx->stream;
+    ZK_HIP(hipMemcpyAsync(d_a.p, a, bytes, hipMemcpyHostToDevice, st));
+    if (two) ZK_HIP(hipMemcpyAsync(d_b.p, b, bytes, hipMemcpyHostToDevice, st));
+    k_test_fq12<<<ceil_div(n, 64), 64, 0, st>>>(op, d_a.as<uint64_t>(), d_b.as<uint64_t>(), n, d_out.as<uint64_t>());
+    ZK_LAUNCH_CHECK();
+    ZK_HIP(hipMemcpyAsync(out, d_out.p, bytes, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    return ZK_OK;
+  })
+}
+int zk_test_pairing_gt(zk_ctx* ctx, const zk_g1_affine* g1, const zk_g2_affine* g2, size_t n, uint64_t* out) {
+  if (!ctx || (n && (!g1 || !g2 || !out))) return ZK_ERR_ARG;
+  if (!n) return ZK_OK;
+  ZK_TGUARD(ctx, {
+    DevBuf d_g1, d_g2, d_out;
+    d_g1.ensure(sizeof(zk_g1_affine) * n);
+    d_g2.ensure(sizeof(zk_g2_affine) * n);
+    d_out.ensure(8 * 72 * n);
+    hipStream_t st = ctx->stream;
+    ZK_HIP(hipMemcpyAsync(d_g1.p, g1, sizeof(zk_g1_affine) * n, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_g2.p, g2, sizeof(zk_g2_affine) * n, hipMemcpyHostToDevice, st));
+    k_test_pairing_gt<<<ceil_div(n, 64), 64, 0, st>>>(d_g1.as<uint64_t>(), d_g2.as<uint64_t>(), n, d_out.as<uint64_t>());
+    ZK_LAUNCH_CHECK();
+    ZK_HIP(hipMemcpyAsync(out, d_out.p, 8 * 72 * n, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    return ZK_OK;
+  })
 }
 
 int zk_test_pk_info(const zk_pk_dev* pk,uint32_t* win, uint32_t* win_c, uint32_t* shard, uint32_t* nshards) {

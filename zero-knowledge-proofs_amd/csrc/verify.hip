@@ -20,38 +20,9 @@ using namespace zk::host;
 
 namespace {
 
-Fq fq_in(const uint64_t* w) {
-  Fq c;
-  std::memcpy(c.l, w, 48);
-  return to_mont(c);
-}
 void fq_out(const Fq& m, uint64_t* w) {
   const Fq c = from_mont(m);
   std::memcpy(w, c.l, 48);
-}
-
-// ABI point -> host affine; false when a coordinate is not canonical or the
-// point is off the curve (no ark value looks like that)
-bool load(const zk_g1_affine& a, A1& p) {
-  p.inf = a.infinity != 0;
-  p.x = zero();
-  p.y = zero();
-  if (p.inf) return true;
-  if (geq_m(a.x) || geq_m(a.y)) return false;
-  p.x = fq_in(a.x);
-  p.y = fq_in(a.y);
-  return on_curve(p);
-}
-bool load(const zk_g2_affine& a, A2& p) {
-  p.inf = a.infinity != 0;
-  p.x = fq2_zero();
-  p.y = fq2_zero();
-  if (p.inf) return true;
-  for (int k = 0; k < 2; k++)
-    if (geq_m(a.x + 6 * k) || geq_m(a.y + 6 * k)) return false;
-  p.x = {fq_in(a.x), fq_in(a.x + 6)};
-  p.y = {fq_in(a.y), fq_in(a.y + 6)};
-  return on_curve(p);
 }
 
 X<Fq> to_x(const A1& p) { return from_affine(p.x, p.y, p.inf); }

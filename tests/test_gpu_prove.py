@@ -215,6 +215,41 @@ def test_prove_all_ones_witness(ctx, zkp, oracle):
     assert np.array_equal(zkp.Prover.prove(dpk, zkp.Witness(z, 1), r=r, s=s).words, oproof)
 
 
+@pytest.mark.parametrize("removed", ["middle", "trailing"])
+def test_prove_with_identity_h_bases(ctx, zkp, oracle, removed):
+    """The two ways lo64(H) reaches the IC+H scalar vector on one GPU.  An
+    identity h_g1 entry in the middle leaves a compacted H index that is not
+    the position (h_ident false): the quotient writes to its own buffer and a
+    gather at offset count[IC] follows.  Identity entries at the end only
+    shorten the vector (h_ident true, count[H] < n): the quotient writes
+    straight into the scalar vector.  Device-witness and host-witness prove
+    both give the oracle's proof from the same modified key."""
+    import torch
+    n = 1 << 6
+    qap, csr_o, params, r, s, z = _synthetic(zkp, oracle, 6, 0x41D)
+    rc, opk, _ = oracle.setup(csr_o, params, 1, nthreads=8)
+    assert rc == 0
+    assert not (opk.h_g1[:, 12] & 0xff).any()
+    rc, whole = oracle.prove(opk, csr_o, z, 1, r, s)
+    assert rc == 0
+    gone = [n // 2] if removed == "middle" else [n - 3, n - 2, n - 1]
+    opk.h_g1[gone] = 0
+    opk.h_g1[gone, 12] = 1
+    rc, oproof = oracle.prove(opk, csr_o, z, 1, r, s)
+    assert rc == 0
+    assert not np.array_equal(oproof, whole)   # the removed bases carried non-zero coefficients
+    dpk = U.pk_from_oracle(zkp, opk, qap, 1).upload(ctx)
+    try:
+        idx, _, _ = dpk.test_bases(4)
+        assert len(idx) == n - len(gone)
+        assert np.array_equal(idx, np.arange(len(idx))) == (removed == "trailing")
+        dz = torch.from_numpy(z.view(np.int64).copy()).cuda()
+        assert np.array_equal(zkp.Prover.prove_device(dpk, dz.data_ptr(), len(z), 1, r, s).words, oproof)
+        assert np.array_equal(zkp.Prover.prove(dpk, zkp.Witness(z, 1), r=r, s=s).words, oproof)
+    finally:
+        dpk.free()
+
+
 def test_gpu_proof_verifies_when_untruncated(ctx, zkp):
     """The reference's test_simple_proof (core:445-481) end to end on the GPU:
     GPU setup with parameters whose derived scalars stay below 2^64 (so the

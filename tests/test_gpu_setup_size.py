@@ -155,3 +155,57 @@ def test_device_key_equals_oracle_setup_2p20(ctx, zkp, oracle, key_2p20, nshards
         else:
             want = np.nonzero(~_is_identity(ref))[0]
         assert np.array_equal(allidx, want), nm
+
+
+@pytest.fixture(scope="module")
+def key_2p6(ctx, zkp, oracle):
+    qap, csr_o, params, _, _ = _case(zkp, oracle, 6, 0x5E06)
+    rc, opk, _ = oracle.setup(csr_o, params, 1, nthreads=oracle.default_threads())
+    assert rc == 0
+    hpk = zkp.CRS.generate_from_qap(ctx, qap, zkp.SetupParams(*params), 1).pk
+    return qap, params, opk, hpk
+
+
+@pytest.mark.parametrize("nshards", [1, 2, 3, 4, 8])
+def test_setup_and_upload_build_the_same_key_2p6(ctx, zkp, oracle, key_2p6, nshards):
+    """The two ways to a device key -- setup straight into HBM, and the upload
+    of the host key the same setup returns -- hold the same bases at the same
+    positions in every slot and window of every shard (3 shards: contiguous
+    ranges; 2, 4, 8: variables by owner, strided H), and both hold the
+    oracle's key, each non-identity base once across the shards."""
+    qap, params, opk, hpk = key_2p6
+    n = 1 << 6
+    rng = np.random.default_rng(nshards)
+    seen = {slot: [] for slot, _ in SLOTS}
+    for shard in range(nshards):
+        made = zkp.CRS.generate_device(ctx, qap, zkp.SetupParams(*params), 1, shard=shard, nshards=nshards)
+        sent = hpk.upload(ctx, shard=shard, nshards=nshards)
+        try:
+            info = made.test_info()
+            assert info == sent.test_info()
+            assert info == (4, 16, shard, nshards)
+            for slot, _ in SLOTS:
+                for w in range(info[0]):
+                    idx, words, nex = made.test_bases(slot, w)
+                    idx2, words2, nex2 = sent.test_bases(slot, w)
+                    assert np.array_equal(idx, idx2), (slot, shard, w)
+                    assert np.array_equal(words, words2), (slot, shard, w)
+                    assert nex == nex2, (slot, shard, w)
+                idx, words, nex = made.test_bases(slot)
+                assert np.array_equal(words[:len(idx)], _ref_rows(opk, slot, idx)), (slot, shard)
+                if slot == 4:
+                    assert (idx % nshards == shard).all()
+                assert nex == (0 if shard or slot in (3, 4) else (5 if slot in (0, 1) else 1))
+                if shard == 0:
+                    check_extras(oracle, opk, slot, words, len(idx), nex)
+                    check_windows(oracle, made, slot, words[:len(idx)], rng)
+                seen[slot].append(idx)
+        finally:
+            made.free()
+            sent.free()
+    for slot, nm in SLOTS:
+        allidx = np.sort(np.concatenate(seen[slot]).astype(np.int64))
+        ref = getattr(hpk, nm)
+        assert len(ref) == (n if slot == 4 else 3 * n - 1 if slot == 3 else 3 * n + 1)
+        want = np.nonzero(~_is_identity(ref))[0] + (2 if slot == 3 else 0)
+        assert np.array_equal(allidx, want), nm

@@ -3,23 +3,10 @@
 #include <cstring>
 #include <vector>
 
-#include "ctx.hpp"
-
-namespace zk {
-zk_pk_dev* pk_upload(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs_csr* q, uint32_t shard, uint32_t nshards);
-int prove_impl(zk_ctx*, const zk_pk_dev*, const void*, size_t, size_t, const zk_fr*, const zk_fr*, zk_proof*,
-               const zk_fr* z_host = nullptr);
-int prove_partial_impl(zk_ctx*, const zk_pk_dev*, const void*, size_t, size_t, const zk_fr*, const zk_fr*,
-                       zk_prove_partial*);
-int prove_partial_host_impl(zk_ctx*, const zk_pk_dev*, const zk_fr*, size_t, size_t, size_t, const zk_fr*,
-                            const zk_fr*, zk_prove_partial*);
-std::vector<uint64_t> witness_ranges(const zk_ctx*, const zk_pk_dev*);
-int combine_impl(const zk_prove_partial*, size_t, const zk_fr*, const zk_fr*, zk_proof*);
-int setup_impl(zk_ctx*, const zk_r1cs_csr*, const zk_setup_params*, uint64_t, uint32_t, uint32_t, zk_pk*,
-               zk_pk_dev**, zk_vk*);
-void serialize_g1_compressed(const zk_g1_affine& p, uint8_t* out);
-void serialize_g2_compressed(const zk_g2_affine& p, uint8_t* out);
-}  // namespace zk
+#include "host_pairing.hpp"
+#include "key.hpp"
+#include "prove.hpp"
+#include "setup.hpp"
 
 using namespace zk;
 
@@ -168,14 +155,13 @@ __global__ void __launch_bounds__(256) k_check_scalars(const uint64_t* __restric
   uint64_t l[4];
 #pragma unroll
   for (int w = 0; w < 4; w++) l[w] = sc[4 * i + w];
-  const uint64_t R[4] = {0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull,
-                        0x73eda753299d7d48ull};
-  bool lt = false, decided = false;
+  Fr a;
 #pragma unroll
-  for (int w = 3; w >= 0; w--) {
-    if (!decided && l[w] != R[w]) { lt = l[w] < R[w]; decided = true; }
+  for (int w = 0; w < 4; w++) {
+    a.v[2 * w] = (uint32_t)l[w];
+    a.v[2 * w + 1] = (uint32_t)(l[w] >> 32);
   }
-  bool ok = lt;
+  bool ok = fr_lt_r(a);
 #pragma unroll
   for (int w = 0; w < 4; w++) {
     const uint32_t lo = 64 * w;

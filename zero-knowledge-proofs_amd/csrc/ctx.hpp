@@ -35,7 +35,7 @@ struct CsrDev {
 struct zk_ctx {
   int device = 0;
   hipStream_t stream = nullptr;                 // main stream
-  hipStream_t side[zk::NUM_SIDE] = {};          // G2 / IC / A+B1 MSM streams
+  hipStream_t side[zk::NUM_SIDE] = {};          // [0] G2, [1] A+B1 (+ IC's scalars) MSM streams; [2] idle
   hipEvent_t ev_scal = nullptr;                 // witness checked (flags reset)
   hipEvent_t ev_quot = nullptr;                 // quotient done (ZK_OPT_EXCHANGE_FIRST)
   hipEvent_t ev_done[zk::NUM_MSM] = {};         // per-MSM completion (results downloaded)
@@ -108,30 +108,6 @@ struct zk_pk_dev {
   uint64_t vcut[zk::HOST_PARTS + 1] = {};
   uint32_t pcut[zk::HOST_PARTS + 1][zk::NUM_MSM] = {};
 };
-
-namespace zk {
-// Expand every slot's bases into the window-shifted copies the shared-bucket
-// MSM reads.
-void pk_precompute_windows(zk_ctx* ctx, zk_pk_dev& pk);
-// canonical-input checks (prove.hip): a < r on the host; on the device,
-// flags |= 8 when some of the n canonical Fr at d_z is >= r
-bool fr_canonical(const zk_fr& a);
-void check_canonical(const void* d_z, uint64_t n, uint32_t* d_flags, hipStream_t st);
-// vcut and pcut of a finished key (device binary search over its idx vectors)
-void pk_part_cuts(zk_pk_dev& pk, hipStream_t st);
-// the witness ranges of a finished key (its idx vectors and shard) from the
-// host constraint matrices: fills pk.wr_dist
-// (own: var_owner of the key's shape; its variables owned by this shard
-// are added, so every z entry is read -- and checked canonical -- by some rank)
-void pk_witness_ranges(zk_pk_dev& pk, const zk_r1cs_csr* q, const std::vector<uint8_t>& own, hipStream_t st);
-// Which shard holds variable v's A / B1 / B2 / IC bases: with a distributed
-// quotient possible (nshards 2, 4 or 8, n % nshards^2 == 0) the shard whose
-// quotient rows first reference v, so a rank's MSM variables are the ones
-// its quotient rows read anyway and its witness slice is ~1/nshards of z;
-// unreferenced variables by contiguous range.  Empty: contiguous ranges of
-// every base vector.
-std::vector<uint8_t> var_owner(const zk_r1cs_csr* q, uint64_t n, uint32_t nshards);
-}
 
 struct zk_msm_bases {
   int device = 0;

@@ -214,6 +214,21 @@ inline bool load(const zk_g2_affine& a, A2& p) {
   p.y = {fq_in(a.y), fq_in(a.y + 6)};
   return on_curve(p);
 }
+// ABI point -> host XYZZ, unchecked (a key's own points)
+inline X<Fq> x_from_abi(const zk_g1_affine& a) {
+  if (a.infinity) return inf<Fq>();
+  return from_affine(fq_in(a.x), fq_in(a.y), false);
+}
+inline X<Fq2> x_from_abi(const zk_g2_affine& a) {
+  if (a.infinity) return inf<Fq2>();
+  return from_affine(Fq2{fq_in(a.x), fq_in(a.x + 6)}, Fq2{fq_in(a.y), fq_in(a.y + 6)}, false);
+}
 
 }  // namespace host
+
+// ark-serialize compressed encoding of ABI points (verify.hip);
+// fq_canonical_largest: y > (p - 1) / 2
+bool fq_canonical_largest(const uint64_t* c);
+void serialize_g1_compressed(const zk_g1_affine& p, uint8_t* out);
+void serialize_g2_compressed(const zk_g2_affine& p, uint8_t* out);
 }  // namespace zk

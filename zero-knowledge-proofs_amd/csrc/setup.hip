@@ -19,13 +19,12 @@
 #include <mutex>
 #include <vector>
 
-#include "ctx.hpp"
+#include "key.hpp"
+#include "prove.hpp"
 #include "quotient.hpp"
+#include "setup.hpp"
 
 namespace zk {
-
-zk_pk_dev* pk_upload(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs_csr* q, uint32_t shard, uint32_t nshards);
-void csr_upload(CsrDev& d, const zk_r1cs_csr* q, hipStream_t st);
 
 // ---------------------------------------------------- fixed-base tables ---
 // T[w][d] = d * 2^(8w) * G, w < 8, d < 256 (affine, Montgomery); T[w][0] unused.
@@ -36,21 +35,17 @@ struct FbTable {
 };
 
 static host::X<host::Fq> g1_gen_host() {
-  host::X<host::Fq> p;
+  host::X<host::Fq> p{{}, {}, host::one(), host::one()};
   std::memcpy(p.X_.l, G1_GEN_HOSTM, 48);
   std::memcpy(p.Y.l, G1_GEN_HOSTM + 12, 48);
-  p.ZZ = host::one();
-  p.ZZZ = host::one();
   return p;
 }
 static host::X<host::Fq2> g2_gen_host() {
-  host::X<host::Fq2> p;
+  host::X<host::Fq2> p{{}, {}, host::f_one<host::Fq2>(), host::f_one<host::Fq2>()};
   std::memcpy(p.X_.c0.l, G2_GEN_HOSTM, 48);
   std::memcpy(p.X_.c1.l, G2_GEN_HOSTM + 12, 48);
   std::memcpy(p.Y.c0.l, G2_GEN_HOSTM + 24, 48);
   std::memcpy(p.Y.c1.l, G2_GEN_HOSTM + 36, 48);
-  p.ZZ = host::f_one<host::Fq2>();
-  p.ZZZ = host::f_one<host::Fq2>();
   return p;
 }
 
@@ -217,32 +212,17 @@ __global__ void __launch_bounds__(256) k_to_abi_g2(const G2A* __restrict__ in, s
 }
 
 // ------------------------------------------------------------- helpers ---
-template <class C>
-static FbTable<C>& fb_table(int device, hipStream_t st);
-
 static std::mutex g_tab_mu;
-template <>
-FbTable<G1>& fb_table<G1>(int device, hipStream_t st) {
-  static std::map<int, FbTable<G1>> tabs;
+template <class C>
+static FbTable<C>& fb_table(int device, hipStream_t st) {
+  static std::map<int, FbTable<C>> tabs;   // one per group
   std::lock_guard<std::mutex> lk(g_tab_mu);
-  FbTable<G1>& t = tabs[device];
+  FbTable<C>& t = tabs[device];
   if (t.host.empty()) {
-    build_table(g1_gen_host(), t.host);
-    t.dev.ensure(sizeof(G1A) * 2048);
-    ZK_HIP(hipMemcpyAsync(t.dev.p, t.host.data(), sizeof(G1A) * 2048, hipMemcpyHostToDevice, st));
-    ZK_HIP(hipStreamSynchronize(st));
-  }
-  return t;
-}
-template <>
-FbTable<G2>& fb_table<G2>(int device, hipStream_t st) {
-  static std::map<int, FbTable<G2>> tabs;
-  std::lock_guard<std::mutex> lk(g_tab_mu);
-  FbTable<G2>& t = tabs[device];
-  if (t.host.empty()) {
-    build_table(g2_gen_host(), t.host);
-    t.dev.ensure(sizeof(G2A) * 2048);
-    ZK_HIP(hipMemcpyAsync(t.dev.p, t.host.data(), sizeof(G2A) * 2048, hipMemcpyHostToDevice, st));
+    if constexpr (C::ABI_WORDS == 13) build_table(g1_gen_host(), t.host);
+    else build_table(g2_gen_host(), t.host);
+    t.dev.ensure(sizeof(typename C::A) * 2048);
+    ZK_HIP(hipMemcpyAsync(t.dev.p, t.host.data(), sizeof(typename C::A) * 2048, hipMemcpyHostToDevice, st));
     ZK_HIP(hipStreamSynchronize(st));
   }
   return t;
@@ -322,6 +302,38 @@ static void csr_to_csc(uint64_t nc, uint64_t V, const uint64_t* rp, const uint32
     }
 }
 
+static Fr fr_dev(const host::Fr& h) {
+  Fr d;
+  const host::Fr v = host::fr_to_dev(h);
+  std::memcpy(d.v, v.l, 32);
+  return d;
+}
+// Z(t) = t^n - 1 over the size-2^log_n domain
+static host::Fr vanishing_at(const host::Fr& t, uint32_t log_n) {
+  host::Fr tn = t;
+  for (uint32_t i = 0; i < log_n; i++) tn = host::fr_mul(tn, tn);
+  return host::fr_sub(tn, host::fr_one());
+}
+// wpow[j] = w^j and L[j] = L_j(t), j < n = 2^log_n
+static void lagrange_at(const host::Fr& t, uint32_t log_n, DevBuf& wpow, DevBuf& L, hipStream_t st) {
+  const uint64_t n = 1ull << log_n;
+  const host::Fr zt = vanishing_at(t, log_n);
+  wpow.ensure(sizeof(Fr) * n);
+  L.ensure(sizeof(Fr) * n);
+  Fr one_d, w_d;
+  for (int i = 0; i < 8; i++) one_d.v[i] = FrParams::ONE[i];
+  for (int i = 0; i < 8; i++) w_d.v[i] = FR_ROOTS[log_n][i];
+  fr_powers(wpow.as<Fr>(), w_d, one_d, n, st);
+  if (host::fr_is_zero(zt)) {
+    k_lagrange_point<<<ceil_div(n, 256), 256, 0, st>>>(wpow.as<Fr>(), fr_dev(t), n, L.as<Fr>());
+  } else {
+    const host::Fr kk = host::fr_mul(zt, host::fr_inv(host::fr_from_u64(n)));
+    k_lagrange<<<ceil_div(ceil_div(n, LAG_CHUNK), 256), 256, 0, st>>>(wpow.as<Fr>(), fr_dev(t), fr_dev(kk), n,
+                                                                      L.as<Fr>());
+  }
+  ZK_LAUNCH_CHECK();
+}
+
 // ---------------------------------------------------------------- setup ---
 int setup_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_setup_params* P, uint64_t num_public, uint32_t shard,
                uint32_t nshards, zk_pk* pk_host, zk_pk_dev** pk_dev, zk_vk* vk) {
@@ -342,30 +354,12 @@ int setup_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_setup_params* P, uint
   if (log_n > 32) return ZK_ERR_DOMAIN;
   if (V >= 0x80000000ull || n >= 0x80000000ull) return ZK_ERR_ARG;
 
-  auto to_dev = [](const host::Fr& h) { Fr d; const host::Fr v = host::fr_to_dev(h); std::memcpy(d.v, v.l, 32); return d; };
   const host::Fr t = host::fr_from_u64(ta);
-  host::Fr tn = t;
-  for (uint32_t i = 0; i < log_n; i++) tn = host::fr_mul(tn, tn);
-  const host::Fr zt = host::fr_sub(tn, host::fr_one());
-  const host::Fr kk = host::fr_mul(zt, host::fr_inv(host::fr_from_u64(n)));
   const host::Fr dinv = host::fr_inv(host::fr_from_u64(de)), ginv = host::fr_inv(host::fr_from_u64(ga));
 
   // ---- Lagrange basis at tau~ and A_i, B_i, C_i (device) ----
   DevBuf wpow, L, abc[3];
-  wpow.ensure(sizeof(Fr) * n);
-  L.ensure(sizeof(Fr) * n);
-  Fr one_d;
-  for (int i = 0; i < 8; i++) one_d.v[i] = FrParams::ONE[i];
-  Fr w_d;
-  for (int i = 0; i < 8; i++) w_d.v[i] = FR_ROOTS[log_n][i];
-  fr_powers(wpow.as<Fr>(), w_d, one_d, n, st);
-  if (host::fr_is_zero(zt)) {
-    k_lagrange_point<<<ceil_div(n, 256), 256, 0, st>>>(wpow.as<Fr>(), to_dev(t), n, L.as<Fr>());
-  } else {
-    k_lagrange<<<ceil_div(ceil_div(n, LAG_CHUNK), 256), 256, 0, st>>>(wpow.as<Fr>(), to_dev(t), to_dev(kk), n,
-                                                                      L.as<Fr>());
-  }
-  ZK_LAUNCH_CHECK();
+  lagrange_at(t, log_n, wpow, L, st);
   const uint64_t* rps[3] = {q->a_rowptr, q->b_rowptr, q->c_rowptr};
   const uint32_t* cols[3] = {q->a_col, q->b_col, q->c_col};
   const zk_fr* vals[3] = {q->a_val, q->b_val, q->c_val};
@@ -402,17 +396,17 @@ int setup_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_setup_params* P, uint
   sh.ensure(8 * n);
   tp.ensure(sizeof(Fr) * n);
   SetupConsts K;
-  K.al = to_dev(host::fr_from_u64(al));
-  K.be = to_dev(host::fr_from_u64(be));
-  K.dinv = to_dev(dinv);
-  K.ginv = to_dev(ginv);
+  K.al = fr_dev(host::fr_from_u64(al));
+  K.be = fr_dev(host::fr_from_u64(be));
+  K.dinv = fr_dev(dinv);
+  K.ginv = fr_dev(ginv);
   K.V = V;
   K.num_public = num_public;
   k_setup_scalars<<<ceil_div(V, 256), 256, 0, st>>>(abc[0].as<Fr>(), abc[1].as<Fr>(), abc[2].as<Fr>(), K,
                                                     sa.as<uint64_t>(), sb.as<uint64_t>(), sic.as<uint64_t>(),
                                                     svk.as<uint64_t>());
   ZK_LAUNCH_CHECK();
-  fr_powers(tp.as<Fr>(), to_dev(t), to_dev(dinv), n, st);   // t~^i / d~
+  fr_powers(tp.as<Fr>(), fr_dev(t), fr_dev(dinv), n, st);   // t~^i / d~
   k_lo64<<<ceil_div(n, 256), 256, 0, st>>>(tp.as<Fr>(), n, sh.as<uint64_t>());
   ZK_LAUNCH_CHECK();
 
@@ -470,16 +464,7 @@ int setup_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_setup_params* P, uint
   }
 
   // ---- device-resident (optionally sharded) proving key ----
-  std::unique_ptr<zk_pk_dev> d(new zk_pk_dev());
-  d->device = ctx->device;
-  d->V = V;
-  d->nc = nc;
-  d->n = n;
-  d->log_n = log_n;
-  d->num_public = num_public;
-  d->shard = shard;
-  d->nshards = nshards;
-  csr_upload(d->csr, q, st);
+  std::unique_ptr<zk_pk_dev> d = pk_create(ctx, q, num_public, shard, nshards);
   // host copies of the scalar vectors decide which bases are the identity
   // (scalar 0 <=> identity, since every scalar is < 2^64 < r)
   std::vector<uint64_t> ha(V), hb(V), hic(nic), hh(n);
@@ -488,87 +473,30 @@ int setup_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_setup_params* P, uint
   if (nic) ZK_HIP(hipMemcpyAsync(hic.data(), sic.p, 8 * nic, hipMemcpyDeviceToHost, st));
   ZK_HIP(hipMemcpyAsync(hh.data(), sh.p, 8 * n, hipMemcpyDeviceToHost, st));
   ZK_HIP(hipStreamSynchronize(st));
-
-  // this shard's variables (var_owner: those its quotient rows first read),
-  // contiguous shard ranges, or (stride = nshards) positions i = shard mod nshards
   const std::vector<uint8_t> own = var_owner(q, n, nshards);
-  auto build_slot = [&](int slot, bool g2, const std::vector<uint64_t>& hs, const DevBuf& ds, uint64_t len,
-                        uint64_t idx_offset, const std::vector<uint64_t>& extra_words, uint32_t nextra,
-                        bool strided = false) {
-    const bool by_owner = !strided && !own.empty();
-    const uint64_t lo = strided ? std::min<uint64_t>(shard, len) : by_owner ? 0 : len * shard / nshards;
-    const uint64_t hi = strided || by_owner ? len : len * (shard + 1) / nshards;
-    const uint64_t stride = strided ? nshards : 1;
-    std::vector<uint32_t> loc, glob;
-    for (uint64_t i = lo; i < hi; i += stride)
-      if (hs[i] && (!by_owner || own[i + idx_offset] == shard)) {
-        loc.push_back((uint32_t)i);
-        glob.push_back((uint32_t)(i + idx_offset));
-      }
-    const uint32_t cnt = (uint32_t)loc.size();
-    const size_t asz = g2 ? sizeof(G2A) : sizeof(G1A);
-    if (slot == MSM_H) {
-      d->h_ident = true;
-      for (uint32_t k = 0; k < cnt; k++) d->h_ident = d->h_ident && glob[k] == k;
-    }
-    d->count[slot] = cnt;
-    d->extras[slot] = nextra;
-    d->bases[slot].ensure(asz * std::max<uint64_t>(cnt + nextra, 1));
-    d->idx[slot].ensure(sizeof(uint32_t) * std::max<uint32_t>(cnt, 1));
-    DevBuf dloc;
-    dloc.ensure(sizeof(uint32_t) * std::max<uint32_t>(cnt, 1));
-    if (cnt) {
-      ZK_HIP(hipMemcpyAsync(dloc.p, loc.data(), 4 * cnt, hipMemcpyHostToDevice, st));
-      ZK_HIP(hipMemcpyAsync(d->idx[slot].p, glob.data(), 4 * cnt, hipMemcpyHostToDevice, st));
-      if (g2) fixed_base<G2>(ctx, ds.as<uint64_t>(), dloc.as<uint32_t>(), cnt, d->bases[slot].as<G2A>(), st);
-      else fixed_base<G1>(ctx, ds.as<uint64_t>(), dloc.as<uint32_t>(), cnt, d->bases[slot].as<G1A>(), st);
-    }
-    if (nextra) {
-      DevBuf ex;
-      ex.ensure(8 * extra_words.size());
-      ZK_HIP(hipMemcpyAsync(ex.p, extra_words.data(), 8 * extra_words.size(), hipMemcpyHostToDevice, st));
-      if (g2) convert_bases<G2>(ex.as<uint64_t>(), d->bases[slot].as<G2A>() + cnt, nextra, st);
-      else convert_bases<G1>(ex.as<uint64_t>(), d->bases[slot].as<G1A>() + cnt, nextra, st);
-    }
-    ZK_HIP(hipStreamSynchronize(st));
+  const KeyExtras ex = key_extras(shard, alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2);
+  // one base vector: G * (the device scalars at this shard's positions)
+  auto build_slot = [&](const SlotShape& shape, const std::vector<uint64_t>& hs, const DevBuf& ds) {
+    std::vector<uint8_t> zero(hs.size());
+    for (size_t i = 0; i < hs.size(); i++) zero[i] = hs[i] == 0;
+    const std::vector<uint32_t> pos = shard_positions(shape, shard, nshards, own, zero.data(), 1);
+    pk_fill_slot(*d, shape, pos, ex, st, [&](const std::vector<uint32_t>& kept, void* d_out) {
+      DevBuf dpos;
+      dpos.ensure(sizeof(uint32_t) * kept.size());
+      ZK_HIP(hipMemcpyAsync(dpos.p, kept.data(), sizeof(uint32_t) * kept.size(), hipMemcpyHostToDevice, st));
+      if (shape.slot == MSM_B2)
+        fixed_base<G2>(ctx, ds.as<uint64_t>(), dpos.as<uint32_t>(), kept.size(), static_cast<G2A*>(d_out), st);
+      else
+        fixed_base<G1>(ctx, ds.as<uint64_t>(), dpos.as<uint32_t>(), kept.size(), static_cast<G1A*>(d_out), st);
+      ZK_HIP(hipStreamSynchronize(st));  // dpos dies here
+    });
   };
-  // extras on shard 0 (see prove.hip): alpha_1 + 2^(64k) delta_1; beta_2 + 2^(64k) delta_2; beta_1
-  std::vector<uint64_t> exA, exB2, exB1, none;
-  uint32_t nA = 0, nB2 = 0, nB1 = 0;
-  if (shard == 0) {
-    auto push = [](std::vector<uint64_t>& v, const void* p, int words) {
-      const uint64_t* w = reinterpret_cast<const uint64_t*>(p);
-      v.insert(v.end(), w, w + words);
-    };
-    push(exA, &alpha_g1, 13);
-    auto dA = host::mul_scalar(G1h, P->delta.l);
-    for (int k = 0; k < 4; k++) {
-      uint64_t w[13];
-      host_to_abi<G1>(dA, w);
-      exA.insert(exA.end(), w, w + 13);
-      for (int b = 0; b < 64; b++) dA = host::dbl(dA);
-    }
-    push(exB2, &beta_g2, 25);
-    auto dB = host::mul_scalar(G2h, P->delta.l);
-    for (int k = 0; k < 4; k++) {
-      uint64_t w[25];
-      host_to_abi<G2>(dB, w);
-      exB2.insert(exB2.end(), w, w + 25);
-      for (int b = 0; b < 64; b++) dB = host::dbl(dB);
-    }
-    push(exB1, &beta_g1, 13);
-    nA = 5;
-    nB2 = 5;
-    nB1 = 1;
-  }
-  build_slot(MSM_A, false, ha, sa, V, 0, exA, nA);
-  build_slot(MSM_B2, true, hb, sb, V, 0, exB2, nB2);
-  build_slot(MSM_B1, false, hb, sb, V, 0, exB1, nB1);
-  build_slot(MSM_IC, false, hic, sic, nic, num_public + 1, none, 0);
-  build_slot(MSM_H, false, hh, sh, n, 0, none, 0, /*strided*/ true);
-  pk_precompute_windows(ctx, *d);
-  pk_witness_ranges(*d, q, own, st);
-  pk_part_cuts(*d, st);
+  build_slot({MSM_A, V, 0, false}, ha, sa);
+  build_slot({MSM_B2, V, 0, false}, hb, sb);
+  build_slot({MSM_B1, V, 0, false}, hb, sb);
+  build_slot({MSM_IC, nic, num_public + 1, false}, hic, sic);
+  build_slot({MSM_H, n, 0, true}, hh, sh);
+  pk_finish(ctx, *d, q, own, st);
   *pk_dev = d.release();
   return ZK_OK;
 }
@@ -626,31 +554,14 @@ int qap_evaluate_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_fr* point, con
   uint64_t n = 1;
   while (n < nc) n <<= 1;
   const uint32_t log_n = (uint32_t)__builtin_ctzll(n);
-  auto to_dev = [](const host::Fr& h) { Fr d; const host::Fr v = host::fr_to_dev(h); std::memcpy(d.v, v.l, 32); return d; };
   const host::Fr t = host::fr_to_mont(point->l);
-  host::Fr tn = t;
-  for (uint32_t i = 0; i < log_n; i++) tn = host::fr_mul(tn, tn);
-  const host::Fr zt = host::fr_sub(tn, host::fr_one());
-  host::fr_from_mont(zt, out[3].l);
+  host::fr_from_mont(vanishing_at(t, log_n), out[3].l);
   for (int k = 0; k < 3; k++) std::memset(out[k].l, 0, 32);
   if (nc == 0) return ZK_OK;
   DevBuf wpow, L, dz, rows;
   CsrDev csr;
   csr_upload(csr, q, st);
-  wpow.ensure(sizeof(Fr) * n);
-  L.ensure(sizeof(Fr) * n);
-  Fr one_d, w_d;
-  for (int i = 0; i < 8; i++) one_d.v[i] = FrParams::ONE[i];
-  for (int i = 0; i < 8; i++) w_d.v[i] = FR_ROOTS[log_n][i];
-  fr_powers(wpow.as<Fr>(), w_d, one_d, n, st);
-  if (host::fr_is_zero(zt)) {
-    k_lagrange_point<<<ceil_div(n, 256), 256, 0, st>>>(wpow.as<Fr>(), to_dev(t), n, L.as<Fr>());
-  } else {
-    const host::Fr kk = host::fr_mul(zt, host::fr_inv(host::fr_from_u64(n)));
-    k_lagrange<<<ceil_div(ceil_div(n, LAG_CHUNK), 256), 256, 0, st>>>(wpow.as<Fr>(), to_dev(t), to_dev(kk), n,
-                                                                      L.as<Fr>());
-  }
-  ZK_LAUNCH_CHECK();
+  lagrange_at(t, log_n, wpow, L, st);
   dz.ensure(sizeof(zk_fr) * std::max<size_t>(zlen, 1));
   if (zlen) ZK_HIP(hipMemcpyAsync(dz.p, z, sizeof(zk_fr) * zlen, hipMemcpyHostToDevice, st));
   rows.ensure(sizeof(Fr) * 3 * nc);
@@ -659,44 +570,4 @@ int qap_evaluate_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_fr* point, con
   for (int k = 0; k < 3; k++) fr_sum_to_host(rows.as<Fr>() + k * nc, nc, &out[k], st);
   return ZK_OK;
 }
-
-// ------------------------------------------------------- serialization ---
-// ark-serialize 0.4 / zcash compressed encoding (ark-bls12-381 0.4): big-endian
-// x with flags in byte 0: 0x80 compressed, 0x40 infinity, 0x20 y > (p-1)/2
-// (Fq2: compare c1, or c0 when c1 == 0).
-static void be48(const uint64_t* l, uint8_t* o) {
-  for (int i = 0; i < 48; i++) o[i] = (uint8_t)(l[(47 - i) / 8] >> (8 * ((47 - i) % 8)));
-}
-bool fq_canonical_largest(const uint64_t* c) {
-  const uint64_t* m = host::FQ().m;
-  uint64_t half[6];
-  for (int i = 0; i < 6; i++) half[i] = (m[i] >> 1) | (i < 5 ? (m[i + 1] << 63) : 0);
-  for (int i = 5; i >= 0; i--) {
-    if (c[i] > half[i]) return true;
-    if (c[i] < half[i]) return false;
-  }
-  return false;
-}
-static bool is_zero6(const uint64_t* c) {
-  uint64_t x = 0;
-  for (int i = 0; i < 6; i++) x |= c[i];
-  return x == 0;
-}
-void serialize_g1_compressed(const zk_g1_affine& p, uint8_t* out) {
-  std::memset(out, 0, 48);
-  if (p.infinity) { out[0] = 0xc0; return; }
-  be48(p.x, out);
-  out[0] |= 0x80;
-  if (fq_canonical_largest(p.y)) out[0] |= 0x20;
-}
-void serialize_g2_compressed(const zk_g2_affine& p, uint8_t* out) {
-  std::memset(out, 0, 96);
-  if (p.infinity) { out[0] = 0xc0; return; }
-  be48(p.x + 6, out);
-  be48(p.x, out + 48);
-  out[0] |= 0x80;
-  const bool big = is_zero6(p.y + 6) ? fq_canonical_largest(p.y) : fq_canonical_largest(p.y + 6);
-  if (big) out[0] |= 0x20;
-}
-
 }  // namespace zk

@@ -1,0 +1,14 @@
+// setup.hpp -- what setup.hip gives the C ABI (capi.hip, util.hip) and the
+// test library (testhooks.hip).
+#pragma once
+#include "ctx.hpp"
+
+namespace zk {
+// pk_host: the whole key into the caller's arrays; else *pk_dev: this shard's
+// device key.  vk (optional) either way.
+int setup_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_setup_params* P, uint64_t num_public, uint32_t shard,
+               uint32_t nshards, zk_pk* pk_host, zk_pk_dev** pk_dev, zk_vk* vk);
+int qap_evaluate_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_fr* point, const zk_fr* z, size_t zlen,
+                      zk_fr out[4]);
+void bases_to_abi_host(bool g2, const void* d_in, uint32_t stride, size_t n, uint64_t* host_out, hipStream_t st);
+}  // namespace zk

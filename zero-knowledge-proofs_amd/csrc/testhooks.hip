@@ -8,13 +8,9 @@
 #include "ctx.hpp"
 #include "pairing.hpp"
 #include "points.hpp"
+#include "prove.hpp"
+#include "setup.hpp"
 #include "../../include/zkp_test.h"
-
-namespace zk {
-void bases_to_abi_host(bool g2, const void* d_in, uint32_t stride, size_t n, uint64_t* host_out, hipStream_t st);
-int prove_virtual_shards_impl(zk_ctx*, const zk_pk_dev* const*, uint32_t, const void*, size_t, size_t,
-                              const zk_fr*, const zk_fr*, zk_proof*);
-}  // namespace zk
 
 using namespace zk;
 

@@ -4,16 +4,14 @@
 //
 // Host code only (no kernels): a verification is four Miller loops and one
 // final exponentiation of strictly sequential field arithmetic
-// (host_pairing.hpp).  Every entry point works without a GPU.
+// (host_pairing.hpp).  Every entry point works without a GPU.  The compressed
+// encoders of the C ABI (zk_proof_serialize_compressed, zk_g*_compress) sit
+// beside the decoders.
 #include <cstring>
 #include <vector>
 
 #include "common.hpp"
 #include "host_pairing.hpp"
-
-namespace zk {
-bool fq_canonical_largest(const uint64_t* c);   // setup.hip: y > (p - 1) / 2
-}
 
 using namespace zk;
 using namespace zk::host;
@@ -156,6 +154,42 @@ int decode_g2(const uint8_t* in, zk_g2_affine& out) {
 }
 
 }  // namespace
+
+namespace zk {
+// ------------------------------------------------------- serialization ---
+// ark-serialize 0.4 / zcash compressed encoding (ark-bls12-381 0.4): big-endian
+// x with flags in byte 0: 0x80 compressed, 0x40 infinity, 0x20 y > (p-1)/2
+// (Fq2: compare c1, or c0 when c1 == 0).
+static void be48(const uint64_t* l, uint8_t* o) {
+  for (int i = 0; i < 48; i++) o[i] = (uint8_t)(l[(47 - i) / 8] >> (8 * ((47 - i) % 8)));
+}
+bool fq_canonical_largest(const uint64_t* c) {
+  const uint64_t* m = host::FQ().m;
+  uint64_t half[6];
+  for (int i = 0; i < 6; i++) half[i] = (m[i] >> 1) | (i < 5 ? (m[i + 1] << 63) : 0);
+  for (int i = 5; i >= 0; i--) {
+    if (c[i] > half[i]) return true;
+    if (c[i] < half[i]) return false;
+  }
+  return false;
+}
+void serialize_g1_compressed(const zk_g1_affine& p, uint8_t* out) {
+  std::memset(out, 0, 48);
+  if (p.infinity) { out[0] = 0xc0; return; }
+  be48(p.x, out);
+  out[0] |= 0x80;
+  if (fq_canonical_largest(p.y)) out[0] |= 0x20;
+}
+void serialize_g2_compressed(const zk_g2_affine& p, uint8_t* out) {
+  std::memset(out, 0, 96);
+  if (p.infinity) { out[0] = 0xc0; return; }
+  be48(p.x + 6, out);
+  be48(p.x, out + 48);
+  out[0] |= 0x80;
+  const bool big = is_zero6(p.y + 6) ? fq_canonical_largest(p.y) : fq_canonical_largest(p.y + 6);
+  if (big) out[0] |= 0x20;
+}
+}  // namespace zk
 
 #define ZK_HOST_GUARD(...)                 \
   try {                                    \

@@ -143,7 +143,12 @@ int zk_ctx_set_schedule(zk_ctx *ctx, int schedule);
  *   ZK_OPT_PROVE_WIN_C    0 by size (default: 16, or 22 from 2^24 constraints
  *                         per key shard), 16 or 22: digit window width of
  *                         the prove MSMs of keys uploaded / set up after the
- *                         call
+ *                         call; governs 64-bit (reference-mode) keys only
+ *   ZK_OPT_SOUND_WIN_C    0 the default (20), 16, 20 or 22: digit window width
+ *                         of the 255-bit prove MSMs of sound keys
+ *                         (zk_groth16_setup_sound_dev, zk_pk_upload_sound)
+ *                         made after the call: ceil(255 / c) window copies
+ *                         of every base; independent of ZK_OPT_PROVE_WIN_C
  *   ZK_OPT_EXCHANGE_TIMEOUT_MS  watchdog of the attached exchange (default
  *                         60000, >= 1): a distributed-quotient proof whose
  *                         peers do not answer within it fails with
@@ -174,7 +179,7 @@ int zk_ctx_set_schedule(zk_ctx *ctx, int schedule);
  * -- live in a separate library, include/zkp_test.h.) */
 enum { ZK_OPT_QUOTIENT_PATH = 1, ZK_OPT_PROVE_WIN_C = 2, ZK_OPT_EXCHANGE_TIMEOUT_MS = 3,
        ZK_OPT_DIST_QUOTIENT = 5, ZK_OPT_EXCHANGE_FIRST = 6, ZK_OPT_POINT_CHUNK = 7,
-       ZK_OPT_VERIFY_CHUNK = 8 };
+       ZK_OPT_VERIFY_CHUNK = 8, ZK_OPT_SOUND_WIN_C = 9 };
 int zk_ctx_set_option(zk_ctx *ctx, int option, int64_t value);
 
 /* ---------------------------------------------------------------- MSM --- */
@@ -239,6 +244,48 @@ int zk_groth16_setup(zk_ctx *ctx, const zk_r1cs_csr *qap, const zk_setup_params 
 /* Same, but the proving key stays in HBM (no host round trip); vk may be NULL. */
 int zk_groth16_setup_dev(zk_ctx *ctx, const zk_r1cs_csr *qap, const zk_setup_params *params,
                          uint64_t num_public, zk_pk_dev **pk_out, zk_vk *vk);
+
+/* --------------------------------------------------------- sound mode --- */
+/* The reference truncates every derived scalar to its low 64 bits and leaves
+ * Z(tau) out of h_g1, so its proofs verify only when every derived scalar is
+ * below 2^64.  Sound mode is textbook Groth16 in the
+ * reference's own arrangement of pi_C, nothing truncated: with l = num_public,
+ * Z(tau) = tau^n - 1,
+ *   a_g1[i] = [A_i(tau)]_1, b_g1[i] = [B_i(tau)]_1, b_g2[i] = [B_i(tau)]_2
+ *   pk ic_g1[i-l-1] = [(beta A_i + alpha B_i + C_i)(tau) / delta]_1, l < i < V
+ *   vk ic_g1[i]     = [(beta A_i + alpha B_i + C_i)(tau) / gamma]_1, i <= l
+ *   h_g1[i] = [tau^i Z(tau) / delta]_1, i < n
+ *   pi_A = alpha_1 + sum z_i a_g1[i] + r delta_1
+ *   pi_B = beta_2 + sum z_i b_g2[i] + s delta_2,  B_1 = beta_1 + sum z_i b_g1[i]
+ *   pi_C = sum_{i>l} z_i ic_g1[i-l-1] + sum H_i h_g1[i] + s pi_A + r B_1
+ * with the whole z_i and the whole quotient coefficients H_i; array lengths,
+ * struct layouts and error rules are those of the reference mode.  A key
+ * carries its mode: the two never mix.
+ *
+ * zk_groth16_setup in sound mode.  Beyond its errors: a parameter >= r is
+ * ZK_ERR_ARG, tau on the evaluation domain (tau^n = 1, so Z(tau) = 0) is
+ * ZK_ERR_SETUP_PARAMS.  No reference counterpart: the reference truncates. */
+int zk_groth16_setup_sound(zk_ctx *ctx, const zk_r1cs_csr *qap, const zk_setup_params *params,
+                           uint64_t num_public, zk_pk *pk, zk_vk *vk);
+/* zk_groth16_setup_dev in sound mode: the device key holds ceil(255 / c)
+ * window copies of every base (ZK_OPT_SOUND_WIN_C; c = 20: 13 copies, 128 B
+ * per G1 and 256 B per G2 point -- about 14 GB at 2^20 constraints of the
+ * synthetic circuit).  A key that does not fit the device comes back as
+ * ZK_ERR_DEVICE with the failed allocation in zk_last_error; more than 2^31
+ * window bases in one MSM as ZK_ERR_ARG.  Never sharded.  No reference
+ * counterpart: the reference truncates. */
+int zk_groth16_setup_sound_dev(zk_ctx *ctx, const zk_r1cs_csr *qap, const zk_setup_params *params,
+                               uint64_t num_public, zk_pk_dev **pk_out, zk_vk *vk);
+/* zk_pk_upload for a key made by zk_groth16_setup_sound.  zk_groth16_prove and
+ * zk_groth16_prove_dev then prove with whole scalars: the device key decides
+ * the mode (a host witness is uploaded whole before the first kernel).
+ * zk_groth16_prove_partial, zk_groth16_prove_partial_host and
+ * zk_groth16_witness_ranges return ZK_ERR_ARG for such a key.  No reference
+ * counterpart: the reference truncates. */
+int zk_pk_upload_sound(zk_ctx *ctx, const zk_pk *pk, const zk_r1cs_csr *qap, zk_pk_dev **out);
+/* 1 for a sound device key, 0 for a reference-mode one (or NULL).  No
+ * reference counterpart. */
+int zk_pk_is_sound(const zk_pk_dev *pk);
 
 /* -------------------------------------------------------------- prove --- */
 /* Upload a proving key + its constraint system once; it stays resident.
@@ -431,6 +478,12 @@ int zk_g2_validate(zk_ctx *ctx, const zk_g2_affine *pts, size_t n, uint8_t *stat
  * below 2^64 (lo64 truncation) -- mirrored, not fixed. */
 int zk_groth16_verify(const zk_vk *vk, const zk_proof *proof, const zk_fr *public_inputs,
                       size_t n_inputs, int *valid);
+/* The same check for a sound key: IC = ic_g1[0] + sum_i x_i ic_g1[i+1] with
+ * every x_i whole.  A public input >= r is ZK_ERR_ARG (the reference mode
+ * ignores the upper limbs; sound mode must not), checked after the input
+ * count.  No reference counterpart: the reference truncates. */
+int zk_groth16_verify_sound(const zk_vk *vk, const zk_proof *proof, const zk_fr *public_inputs,
+                            size_t n_inputs, int *valid);
 /* BatchVerifier::verify_batch (core:360-432) with its Fr::rand coefficients
  * made explicit (coeffs[k] for proof k, canonical): ONE pairing check on
  * sum c_k A_k, sum c_k B_k, sum c_k IC_k, sum c_k C_k -- the reference's rule
@@ -469,6 +522,12 @@ typedef enum {
 int zk_groth16_verify_many(zk_ctx *ctx, const zk_vk *vk, const zk_proof *proofs,
                            const zk_fr *public_inputs, size_t n_inputs, size_t n_proofs,
                            uint8_t *status);
+/* zk_groth16_verify_many for a sound key: status[k] is what
+ * zk_groth16_verify_sound gives for proof k alone, a public input >= r making
+ * that proof MALFORMED.  No reference counterpart: the reference truncates. */
+int zk_groth16_verify_many_sound(zk_ctx *ctx, const zk_vk *vk, const zk_proof *proofs,
+                                 const zk_fr *public_inputs, size_t n_inputs, size_t n_proofs,
+                                 uint8_t *status);
 /* n_products pairing products on the GPU, one lane per product: product j =
  * prod_{i<k} e(g1[jk+i], g2[jk+i]) with k = pairs_per_product; status[j] as
  * above (ACCEPT: the product is 1 -- zk_pairing_product_is_one's *result = 1;

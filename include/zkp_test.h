@@ -36,7 +36,9 @@ int zk_test_fault_after_exchange(zk_ctx *ctx, int k);
  * of the window-shifted copies (w = 0: the bases themselves, w: 2^(win_c w)
  * times them).  *count = compacted non-identity bases of this shard,
  * *nextras = extra bases appended after them (shard 0: alpha_1 and
- * 2^(64k) delta_1 / beta_2 and 2^(64k) delta_2 / beta_1).  With cap >=
+ * 2^(64k) delta_1 / beta_2 and 2^(64k) delta_2 / beta_1; a sound key:
+ * alpha_1, delta_1 / beta_2, delta_2 / beta_1, and ceil(255 / win_c)
+ * windows).  With cap >=
  * count + nextras: idx_out[k] = the variable (H: coefficient) index of base
  * k < count, words_out = all count + nextras bases as canonical ABI words
  * (13 per G1, 25 per G2 point).  cap = 0 only queries the counts. */
@@ -44,6 +46,13 @@ int zk_test_pk_bases(zk_ctx *ctx, const zk_pk_dev *pk, int slot, int window, uin
                      uint64_t *words_out, size_t cap, size_t *count, size_t *nextras);
 /* The key's window plan and shard: win copies of c = win_c bits. */
 int zk_test_pk_info(const zk_pk_dev *pk, uint32_t *win, uint32_t *win_c, uint32_t *shard, uint32_t *nshards);
+/* The 255-bit fixed-base kernel of a sound setup (csrc/setup.hip,
+ * k_fixed_base_wide) on its own, one lane per scalar: out[i] = scalars[i] G
+ * for n whole canonical scalars, G the G1 generator.  A scalar >= r is
+ * ZK_ERR_ARG. */
+int zk_test_fixed_base_g1(zk_ctx *ctx, const zk_fr *scalars, size_t n, zk_g1_affine *out);
+/* Same with the G2 generator. */
+int zk_test_fixed_base_g2(zk_ctx *ctx, const zk_fr *scalars, size_t n, zk_g2_affine *out);
 /* The device square roots behind point decompression (csrc/points.hpp), one
  * lane per element: in = n canonical Fq (6 words each), out = a canonical
  * root where ok[i] = 1 (zeros where the input has none), largest[i] = the

@@ -56,15 +56,18 @@ EXPORTS = (
     "zk_g1_compress", "zk_g2_compress", "zk_g1_decompress", "zk_g2_decompress",
     "zk_g1_validate", "zk_g2_validate",
     "zk_groth16_verify_many", "zk_pairing_products",
+    "zk_groth16_setup_sound", "zk_groth16_setup_sound_dev", "zk_pk_upload_sound", "zk_pk_is_sound",
+    "zk_groth16_verify_sound", "zk_groth16_verify_many_sound",
 )
 # include/zkp_test.h (libzkp_amd_test.so)
 TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fault_after_exchange",
                 "zk_test_pk_bases", "zk_test_pk_info", "zk_test_fq_sqrt", "zk_test_fq2_sqrt",
-                "zk_test_fq12", "zk_test_pairing_gt")
+                "zk_test_fq12", "zk_test_pairing_gt", "zk_test_fixed_base_g1", "zk_test_fixed_base_g2")
 ZK_OPT_QUOTIENT_PATH, ZK_OPT_PROVE_WIN_C, ZK_OPT_EXCHANGE_TIMEOUT_MS, ZK_OPT_DIST_QUOTIENT = 1, 2, 3, 5
 ZK_OPT_EXCHANGE_FIRST = 6
 ZK_OPT_POINT_CHUNK = 7
 ZK_OPT_VERIFY_CHUNK = 8
+ZK_OPT_SOUND_WIN_C = 9
 # zk_verify_status: what a proof / pairing product of a GPU batch call can be
 ZK_VERIFY_REJECT, ZK_VERIFY_ACCEPT, ZK_VERIFY_MALFORMED = range(3)
 # ops of zk_test_fq12 (include/zkp_test.h); FINAL_EXP computes a^(FINAL_EXP_C (p^12 - 1) / r)
@@ -402,7 +405,8 @@ class Context:
     def set_option(self, option, value):
         """zk_ctx_set_option: ZK_OPT_QUOTIENT_PATH (-1 by size, 0 small-domain,
         1 large-domain), ZK_OPT_PROVE_WIN_C (0 by size, 16, 22; keys made
-        afterwards), ZK_OPT_EXCHANGE_TIMEOUT_MS (>= 1), ZK_OPT_DIST_QUOTIENT
+        afterwards), ZK_OPT_SOUND_WIN_C (0 the default, 16, 20, 22; sound
+        keys made afterwards), ZK_OPT_EXCHANGE_TIMEOUT_MS (>= 1), ZK_OPT_DIST_QUOTIENT
         (-1 distributed when an exchange of the key's shape is attached, 0
         replicated), ZK_OPT_EXCHANGE_FIRST (0 MSMs start with the witness, 1
         they wait for the distributed quotient), ZK_OPT_POINT_CHUNK (points
@@ -515,12 +519,14 @@ class Context:
         return self._validate("zk_g2_validate", arr, G2_WORDS)
 
     # ---- batch verification on the GPU (one lane per proof / product) ----
-    def verify_many(self, vk, proofs, inputs):
+    def verify_many(self, vk, proofs, inputs, sound=False):
         """zk_groth16_verify_many: n proofs (Proof objects, or an (n, 51)
         uint64 array of their words) against one vk, inputs an (n, n_inputs,
         4) uint64 array or n rows of ints -> n uint8 ZK_VERIFY_* statuses,
         each what Verifier.verify says for that proof alone (MALFORMED where
-        it raises ValueError).  InvalidWitness when n_inputs != vk.num_public."""
+        it raises ValueError).  InvalidWitness when n_inputs != vk.num_public.
+        sound: zk_groth16_verify_many_sound -- the whole public inputs, one
+        >= r making its proof MALFORMED."""
         if isinstance(proofs, np.ndarray):
             pw = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 2 * G1_WORDS + G2_WORDS)
         else:
@@ -538,11 +544,22 @@ class Context:
         if len(inp) != n or inp.shape[2] != 4:
             raise ValueError("verify_many: one row of public inputs (n_inputs x 4 words) per proof")
         st = np.zeros(n, dtype=np.uint8)
-        rc = lib().zk_groth16_verify_many(C.c_void_p(self._h), C.byref(vk.s), _p(pw) if n else None,
-                                          _p(inp) if inp.size else None, C.c_size_t(inp.shape[1]), C.c_size_t(n),
-                                          _p(st) if n else None)
+        fn = lib().zk_groth16_verify_many_sound if sound else lib().zk_groth16_verify_many
+        rc = fn(C.c_void_p(self._h), C.byref(vk.s), _p(pw) if n else None, _p(inp) if inp.size else None,
+                C.c_size_t(inp.shape[1]), C.c_size_t(n), _p(st) if n else None)
         _check(rc, self, "zk_groth16_verify_many")
         return st
+
+    def test_fixed_base(self, scalars, g2=False):
+        """zk_test_fixed_base_g1 / _g2 (test library): scalars (ints, or (n, 4)
+        uint64 canonical limbs) -> (n, 13 | 25) words of scalar * generator
+        through the 255-bit fixed-base kernel of a sound setup."""
+        sc = _fr_rows(scalars)
+        out = np.zeros((max(len(sc), 1), G2_WORDS if g2 else G1_WORDS), dtype=np.uint64)
+        fn = test_lib().zk_test_fixed_base_g2 if g2 else test_lib().zk_test_fixed_base_g1
+        _check(fn(C.c_void_p(self._h), _p(sc) if len(sc) else None, C.c_size_t(len(sc)), _p(out)), self,
+               "zk_test_fixed_base")
+        return out[:len(sc)]
 
     def pairing_products(self, g1_points, g2_points, pairs_per_product):
         """zk_pairing_products: product j = prod_{i<k} e(g1[jk+i], g2[jk+i])
@@ -890,9 +907,12 @@ def _key_fields(key, table):
 
 
 class ProvingKey:
-    """crates/groth16-setup/src/lib.rs:27-52 (host arrays, canonical affine)."""
+    """crates/groth16-setup/src/lib.rs:27-52 (host arrays, canonical affine).
+    sound: made by a sound setup (whole scalars, Z(tau) in h_g1); upload()
+    and the key files carry the flag, so a key never changes mode."""
 
-    def __init__(self, V, n, num_public, qap):
+    def __init__(self, V, n, num_public, qap, sound=False):
+        self.sound = bool(sound)
         self.a_g1 = np.zeros((V, G1_WORDS), dtype=np.uint64)
         self.b_g1 = np.zeros((V, G1_WORDS), dtype=np.uint64)
         self.b_g2 = np.zeros((V, G2_WORDS), dtype=np.uint64)
@@ -932,9 +952,11 @@ class ProvingKey:
 
 
 class VerificationKey:
-    """crates/groth16-setup/src/lib.rs:56-69"""
+    """crates/groth16-setup/src/lib.rs:56-69.  sound: made by a sound setup;
+    Verifier dispatches on it."""
 
-    def __init__(self, num_public):
+    def __init__(self, num_public, sound=False):
+        self.sound = bool(sound)
         self.ic_g1 = np.zeros((num_public + 1, G1_WORDS), dtype=np.uint64)
         self.num_public = num_public
         self.s = _VK()
@@ -943,10 +965,10 @@ class VerificationKey:
         self.s.num_public = num_public
 
     @classmethod
-    def from_points(cls, alpha_g1, beta_g2, gamma_g2, delta_g2, ic_g1):
+    def from_points(cls, alpha_g1, beta_g2, gamma_g2, delta_g2, ic_g1, sound=False):
         """Build from canonical affine words (13 per G1, 25 per G2 point)."""
         ic = np.asarray(ic_g1, dtype=np.uint64).reshape(-1, G1_WORDS)
-        vk = cls(len(ic) - 1)
+        vk = cls(len(ic) - 1, sound)
         vk.ic_g1[:] = ic
         for name, words in (("alpha_g1", alpha_g1), ("beta_g2", beta_g2), ("gamma_g2", gamma_g2),
                             ("delta_g2", delta_g2)):
@@ -976,13 +998,22 @@ class DeviceProvingKey:
     def upload(cls, ctx, pk, shard=0, nshards=1):
         h = C.c_void_p()
         s = pk._bind()
-        if nshards == 1:
+        if getattr(pk, "sound", False):
+            if nshards != 1:
+                raise ValueError("a sound proving key cannot be sharded (nshards must be 1)")
+            rc = lib().zk_pk_upload_sound(C.c_void_p(ctx._h), C.byref(s), C.byref(pk.qap.csr.s), C.byref(h))
+        elif nshards == 1:
             rc = lib().zk_pk_upload(C.c_void_p(ctx._h), C.byref(s), C.byref(pk.qap.csr.s), C.byref(h))
         else:
             rc = lib().zk_pk_upload_shard(C.c_void_p(ctx._h), C.byref(s), C.byref(pk.qap.csr.s),
                                           C.c_uint32(shard), C.c_uint32(nshards), C.byref(h))
         _check(rc, ctx, "zk_pk_upload")
         return cls(ctx, h.value, pk.qap)
+
+    @property
+    def sound(self):
+        """zk_pk_is_sound: the key proves with whole scalars (a sound setup)."""
+        return bool(lib().zk_pk_is_sound(C.c_void_p(self._h)))
 
     def witness_ranges(self):
         """zk_groth16_witness_ranges: (k, 2) array of the [lo, hi) witness
@@ -1041,29 +1072,43 @@ class CRS:
         self.pk, self.vk = pk, vk
 
     @classmethod
-    def generate_from_qap(cls, ctx, qap, params, num_public):
+    def generate_from_qap(cls, ctx, qap, params, num_public, sound=False):
+        """sound: zk_groth16_setup_sound -- whole scalars and Z(tau) in h_g1
+        (textbook Groth16) instead of the reference's truncated ones; the
+        keys carry .sound.  tau on the evaluation domain is a SetupError."""
         params.validate()
         if num_public >= qap.num_variables:
             raise SetupError("Number of public inputs must be less than total variables")
-        pk = ProvingKey(qap.num_variables, qap.domain_size, num_public, qap)
-        vk = VerificationKey(num_public)
+        pk = ProvingKey(qap.num_variables, qap.domain_size, num_public, qap, sound)
+        vk = VerificationKey(num_public, sound)
         s = pk._bind()
-        rc = lib().zk_groth16_setup(C.c_void_p(ctx._h), C.byref(qap.csr.s), C.byref(params._c()),
-                                    C.c_uint64(num_public), C.byref(s), C.byref(vk.s))
-        _check(rc, ctx, "zk_groth16_setup")
+        fn = lib().zk_groth16_setup_sound if sound else lib().zk_groth16_setup
+        rc = fn(C.c_void_p(ctx._h), C.byref(qap.csr.s), C.byref(params._c()), C.c_uint64(num_public), C.byref(s),
+                C.byref(vk.s))
+        _check(rc, ctx, "zk_groth16_setup_sound" if sound else "zk_groth16_setup")
         return cls(pk, vk)
 
     @classmethod
-    def generate_random(cls, ctx, qap, num_public, rng):
-        return cls.generate_from_qap(ctx, qap, SetupParams.random(rng), num_public)
+    def generate_random(cls, ctx, qap, num_public, rng, sound=False):
+        return cls.generate_from_qap(ctx, qap, SetupParams.random(rng), num_public, sound)
 
     @staticmethod
-    def generate_device(ctx, qap, params, num_public, shard=0, nshards=1):
-        """Setup straight into HBM (no host round trip) -> DeviceProvingKey."""
+    def generate_device(ctx, qap, params, num_public, shard=0, nshards=1, sound=False, vk=None):
+        """Setup straight into HBM (no host round trip) -> DeviceProvingKey.
+        sound: zk_groth16_setup_sound_dev (never sharded).  vk: a
+        VerificationKey(num_public) to fill beside it (unsharded setups)."""
         h = C.c_void_p()
-        if nshards == 1:
+        vkp = C.byref(vk.s) if vk is not None else None
+        if vk is not None and (nshards != 1 or vk.num_public != num_public or bool(vk.sound) != bool(sound)):
+            raise ValueError("generate_device: vk needs an unsharded setup, and its num_public and mode")
+        if sound:
+            if nshards != 1:
+                raise ValueError("a sound proving key cannot be sharded (nshards must be 1)")
+            rc = lib().zk_groth16_setup_sound_dev(C.c_void_p(ctx._h), C.byref(qap.csr.s), C.byref(params._c()),
+                                                  C.c_uint64(num_public), C.byref(h), vkp)
+        elif nshards == 1:
             rc = lib().zk_groth16_setup_dev(C.c_void_p(ctx._h), C.byref(qap.csr.s), C.byref(params._c()),
-                                            C.c_uint64(num_public), C.byref(h), None)
+                                            C.c_uint64(num_public), C.byref(h), vkp)
         else:
             rc = lib().zk_groth16_setup_dev_shard(C.c_void_p(ctx._h), C.byref(qap.csr.s),
                                                   C.byref(params._c()), C.c_uint64(num_public),
@@ -1289,14 +1334,18 @@ def pairing_product_is_one(g1_points, g2_points):
 
 
 class Verifier:
-    """Verifier::verify (crates/groth16-core/src/lib.rs:308-355), on the host."""
+    """Verifier::verify (crates/groth16-core/src/lib.rs:308-355), on the host.
+    A sound vk (vk.sound) goes through zk_groth16_verify_sound /
+    zk_groth16_verify_many_sound: the whole public inputs, one >= r a
+    ValueError."""
 
     @staticmethod
     def verify(vk, proof, public_inputs):
         inp = _fr_rows(public_inputs)
         valid = C.c_int(0)
-        rc = lib().zk_groth16_verify(C.byref(vk.s), C.byref(proof._c()), _p(inp) if len(inp) else None,
-                                     C.c_size_t(len(inp)), C.byref(valid))
+        fn = lib().zk_groth16_verify_sound if getattr(vk, "sound", False) else lib().zk_groth16_verify
+        rc = fn(C.byref(vk.s), C.byref(proof._c()), _p(inp) if len(inp) else None, C.c_size_t(len(inp)),
+                C.byref(valid))
         _check(rc, None, "zk_groth16_verify")
         return bool(valid.value)
 
@@ -1313,10 +1362,12 @@ class Verifier:
         inp = np.zeros((len(rows), vk.num_public, 4), dtype=np.uint64)
         for k, r in enumerate(rows):
             inp[k] = r
-        st = ctx.verify_many(vk, [p for p, _ in proofs_and_inputs], inp)
+        sound = getattr(vk, "sound", False)
+        st = ctx.verify_many(vk, [p for p, _ in proofs_and_inputs], inp, sound=sound)
         bad = np.flatnonzero(st == ZK_VERIFY_MALFORMED)
         if len(bad):
-            raise ValueError(f"verify_many: proof {int(bad[0])} has a point that is not canonical or not on its curve")
+            raise ValueError(f"verify_many: proof {int(bad[0])} has a point that is not canonical or not on its curve"
+                             + (", or a public input that is not below r" if sound else ""))
         return st == ZK_VERIFY_ACCEPT
 
 
@@ -1327,6 +1378,9 @@ class BatchVerifier:
 
     @staticmethod
     def verify_batch(vk, proofs_and_inputs, coeffs=None, rng=None):
+        if getattr(vk, "sound", False):
+            # the reference's one-bit rule is no sound batching in any mode
+            raise ValueError("BatchVerifier is reference-only: verify a sound key's proofs with Verifier.verify_many")
         k = len(proofs_and_inputs)
         if coeffs is None:
             if k and rng is None:
@@ -1369,8 +1423,23 @@ class BatchVerifier:
 #                 multiple of 8, then the CSR section byte for byte as above
 #   verification key: b"ZKAMDVK2", u64 num_public, ic_len, alpha_g1 (48),
 #                 beta_g2, gamma_g2, delta_g2 (96 each), ic_g1 compressed
+# A sound key (key.sound) is written with its own magic -- b"ZKAMDPS1" /
+# b"ZKAMDPS2", verification key b"ZKAMDVS1" / b"ZKAMDVS2" -- over the very
+# same layouts, and load_* sets .sound from it: a key cannot change mode by
+# being saved and loaded.
 _PK_MAGIC, _VK_MAGIC = b"ZKAMDPK1", b"ZKAMDVK1"
 _PK2_MAGIC, _VK2_MAGIC = b"ZKAMDPK2", b"ZKAMDVK2"
+_PKS_MAGIC, _VKS_MAGIC = b"ZKAMDPS1", b"ZKAMDVS1"
+_PKS2_MAGIC, _VKS2_MAGIC = b"ZKAMDPS2", b"ZKAMDVS2"
+# magic -> (compressed, sound)
+_PK_MAGICS = {_PK_MAGIC: (False, False), _PK2_MAGIC: (True, False), _PKS_MAGIC: (False, True),
+              _PKS2_MAGIC: (True, True)}
+_VK_MAGICS = {_VK_MAGIC: (False, False), _VK2_MAGIC: (True, False), _VKS_MAGIC: (False, True),
+              _VKS2_MAGIC: (True, True)}
+
+
+def _magic_of(table, compressed, sound):
+    return next(m for m, v in table.items() if v == (bool(compressed), bool(sound)))
 
 
 def _u64s(f, k):
@@ -1406,7 +1475,7 @@ def _read_compressed(f, path, ctx, table, counts):
 
 def save_proving_key(pk, path, compressed=False):
     with open(path, "wb") as f:
-        f.write(_PK2_MAGIC if compressed else _PK_MAGIC)
+        f.write(_magic_of(_PK_MAGICS, compressed, getattr(pk, "sound", False)))
         csr = pk.qap.csr
         np.array([pk.qap.num_variables, pk.qap.domain_size, pk.num_public, csr.num_constraints,
                   len(pk.a_g1), len(pk.b_g1), len(pk.b_g2), len(pk.ic_g1), len(pk.h_g1)], dtype="<u8").tofile(f)
@@ -1430,17 +1499,19 @@ def save_proving_key(pk, path, compressed=False):
 
 
 def load_proving_key(path, ctx=None, validate=False):
-    """Read a ZKAMDPK1 or ZKAMDPK2 file (picked by its magic).  A compressed
+    """Read a ZKAMDPK1 or ZKAMDPK2 file (picked by its magic; ZKAMDPS1 /
+    ZKAMDPS2: the same layouts for a sound key, which sets .sound).  A compressed
     file is decompressed on the GPU of `ctx` (default_context() when None),
     which validates every point; an uncompressed one is read as it is, and
     checked by ProvingKey.validate(ctx) only with validate=True.  An invalid
     point raises ValueError("<path>: <field>[<index>]: <reason>")."""
     with open(path, "rb") as f:
         magic = f.read(8)
-        if magic not in (_PK_MAGIC, _PK2_MAGIC):
+        if magic not in _PK_MAGICS:
             raise ValueError(f"{path}: not a proving key file")
+        compressed, sound = _PK_MAGICS[magic]
         V, n, npub, nc, la, lb, lb2, lic, lh = (int(x) for x in _u64s(f, 9))
-        if magic == _PK2_MAGIC:
+        if compressed:
             got = _read_compressed(f, path, ctx, _PK_FIELDS, (1, 1, 1, 1, 1, la, lb, lb2, lic, lh))
             pts, arrs = [a.reshape(-1) for a in got[:5]], got[5:]
             _read_exact(f, -f.tell() % 8)
@@ -1462,13 +1533,13 @@ def load_proving_key(path, ctx=None, validate=False):
     qap = QAP(CSRMatrices(nc, V, mats))
     if qap.domain_size != n:
         raise ValueError("key domain does not match its constraint system")
-    pk = ProvingKey(0, 0, npub, qap)
+    pk = ProvingKey(0, 0, npub, qap, sound)
     pk.a_g1, pk.b_g1, pk.b_g2, pk.ic_g1, pk.h_g1 = (np.ascontiguousarray(a, dtype=np.uint64) for a in arrs)
     for nm, words in zip(("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2"), pts):
         field = getattr(pk.s, nm)
         for i, w in enumerate(words):
             field.w[i] = int(w)
-    if validate and magic == _PK_MAGIC:
+    if validate and not compressed:
         _validate_loaded(pk, path, ctx)
     return pk
 
@@ -1482,7 +1553,7 @@ def _validate_loaded(key, path, ctx):
 
 def save_verification_key(vk, path, compressed=False):
     with open(path, "wb") as f:
-        f.write(_VK2_MAGIC if compressed else _VK_MAGIC)
+        f.write(_magic_of(_VK_MAGICS, compressed, getattr(vk, "sound", False)))
         np.array([vk.num_public, len(vk.ic_g1)], dtype="<u8").tofile(f)
         if compressed:
             _write_compressed(f, vk, _VK_FIELDS)
@@ -1493,21 +1564,23 @@ def save_verification_key(vk, path, compressed=False):
 
 
 def load_verification_key(path, ctx=None, validate=False):
-    """Read a ZKAMDVK1 or ZKAMDVK2 file; see load_proving_key."""
+    """Read a ZKAMDVK1 or ZKAMDVK2 file (ZKAMDVS1 / ZKAMDVS2: a sound key);
+    see load_proving_key."""
     with open(path, "rb") as f:
         magic = f.read(8)
-        if magic not in (_VK_MAGIC, _VK2_MAGIC):
+        if magic not in _VK_MAGICS:
             raise ValueError(f"{path}: not a verification key file")
+        compressed, sound = _VK_MAGICS[magic]
         npub, lic = (int(x) for x in _u64s(f, 2))
-        if magic == _VK2_MAGIC:
+        if compressed:
             got = _read_compressed(f, path, ctx, _VK_FIELDS, (1, 1, 1, 1, lic))
             pts, ic = [a.reshape(-1) for a in got[:4]], got[4]
         else:
             pts = [_u64s(f, G1_WORDS)] + [_u64s(f, G2_WORDS) for _ in range(3)]
             ic = _u64s(f, lic * G1_WORDS).reshape(lic, G1_WORDS)
-    vk = VerificationKey.from_points(*pts, ic)
+    vk = VerificationKey.from_points(*pts, ic, sound=sound)
     vk.num_public = vk.s.num_public = npub
-    if validate and magic == _VK_MAGIC:
+    if validate and not compressed:
         _validate_loaded(vk, path, ctx)
     return vk
 

@@ -446,7 +446,28 @@ int zk_groth16_setup_dev_shard(zk_ctx* ctx, const zk_r1cs_csr* qap, const zk_set
   ZK_GUARD(ctx, { return setup_impl(ctx, qap, params, num_public, shard, nshards, nullptr, out, nullptr); })
 }
 
+// sound mode: whole scalars, Z(tau) in the H query (setup.hip)
+int zk_groth16_setup_sound(zk_ctx* ctx, const zk_r1cs_csr* qap, const zk_setup_params* params, uint64_t num_public,
+                           zk_pk* pk, zk_vk* vk) {
+  if (!ctx || !qap || !params || !pk || !vk) return ZK_ERR_ARG;
+  ZK_GUARD(ctx, { return setup_impl(ctx, qap, params, num_public, 0, 1, pk, nullptr, vk, true); })
+}
+int zk_groth16_setup_sound_dev(zk_ctx* ctx, const zk_r1cs_csr* qap, const zk_setup_params* params,
+                               uint64_t num_public, zk_pk_dev** out, zk_vk* vk) {
+  if (!ctx || !qap || !params || !out) return ZK_ERR_ARG;
+  ZK_GUARD(ctx, { return setup_impl(ctx, qap, params, num_public, 0, 1, nullptr, out, vk, true); })
+}
+
 // ---------------------------------------------------------------- prove ---
+int zk_pk_upload_sound(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs_csr* qap, zk_pk_dev** out) {
+  if (!ctx || !pk || !qap || !out) return ZK_ERR_ARG;
+  ZK_GUARD(ctx, {
+    *out = pk_upload(ctx, pk, qap, 0, 1, true);
+    return ZK_OK;
+  })
+}
+int zk_pk_is_sound(const zk_pk_dev* pk) { return pk && pk->sound() ? 1 : 0; }
+
 int zk_pk_upload(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs_csr* qap, zk_pk_dev** out) {
   if (!ctx || !pk || !qap || !out) return ZK_ERR_ARG;
   ZK_GUARD(ctx, {
@@ -552,6 +573,10 @@ int zk_ctx_attach_exchange(zk_ctx* ctx, const zk_exchange_ops* ops, int rank, in
 
 int zk_groth16_witness_ranges(zk_ctx* ctx, const zk_pk_dev* pk, uint64_t* ranges, size_t cap, size_t* nranges) {
   if (!ctx || !pk || !nranges || (cap && !ranges)) return ZK_ERR_ARG;
+  if (pk->sound()) {
+    ctx->err = "a sound proving key is never sharded: it has no witness ranges";
+    return ZK_ERR_ARG;
+  }
   const std::vector<uint64_t> w = witness_ranges(ctx, pk);
   *nranges = w.size() / 2;
   for (size_t k = 0; k < std::min(cap, w.size() / 2); k++) {

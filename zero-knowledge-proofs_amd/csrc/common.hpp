@@ -52,7 +52,15 @@ struct DevBuf {
   void ensure(size_t b) {
     if (b <= bytes) return;
     release();
-    ZK_HIP(hipMalloc(&p, b ? b : 16));
+    // a failed allocation (a key too large for the device) is an Error like
+    // any other HIP failure; the runtime's last-error word is cleared so that
+    // the next launch check of this thread does not report it a second time
+    const hipError_t e = hipMalloc(&p, b ? b : 16);
+    if (e != hipSuccess) {
+      p = nullptr;
+      (void)hipGetLastError();
+      throw Error(ZK_ERR_DEVICE, "hipMalloc of " + std::to_string(b) + " bytes: " + hipGetErrorString(e));
+    }
     bytes = b;
   }
   template <class T>

@@ -61,6 +61,7 @@ struct zk_ctx {
   int sched = 0;                               // 0 overlapped streams, 3 serial (per-kernel timing)
   int quot_path = -1;                          // -1 by domain size, 0 small-domain, 1 large-domain
   int prove_win_c = 0;                         // 0 by size, else 16 or 22 (keys made after the call)
+  int sound_win_c = 0;                         // sound keys: 0 the default, else 16, 20 or 22 (likewise)
   double exch_timeout_ms = 60000;              // watchdog of an attached exchange
   int dist_quotient = -1;                      // -1 distributed when an exchange of the key's shape
                                                // is attached, 0 never (each rank the whole quotient)
@@ -76,6 +77,12 @@ struct zk_pk_dev {
   uint64_t V = 0, n = 0, nc = 0, num_public = 0;
   uint32_t log_n = 0;
   uint32_t shard = 0, nshards = 1;
+  // Width of every prove scalar: 64 (the reference's lo64 truncation) or 255
+  // (a sound key: whole canonical Fr, zk_groth16_setup_sound / zk_pk_upload_sound).
+  // It decides the extras, the window count and the prove path; a sound key
+  // is never sharded.
+  uint32_t scalar_bits = 64;
+  bool sound() const { return scalar_bits > 64; }
   zk::CsrDev csr;
   // Compacted non-identity bases (device Montgomery affine) followed by the
   // shard-0 extras, and the variable index feeding each base's scalar.
@@ -84,7 +91,8 @@ struct zk_pk_dev {
   uint32_t count[zk::NUM_MSM] = {};  // compacted bases (without extras)
   uint32_t extras[zk::NUM_MSM] = {}; // extra bases appended (shard 0 only)
   // Window-shifted base copies (msm_precompute_windows): bases[slot] holds
-  // win x (count + extras) points, window w = 2^(win_c w) x the base.
+  // win x (count + extras) points, window w = 2^(win_c w) x the base,
+  // win = ceil(scalar_bits / win_c).
   // The IC and H vectors are ONE MSM of the prove (both terms of pi_C):
   // bases[MSM_H] holds win x (count[IC] + count[H]) points, each window the
   // IC bases then the H bases (ich_tot() per window), and bases[MSM_IC] is

@@ -43,9 +43,11 @@ void csr_upload(CsrDev& d, const zk_r1cs_csr* q, hipStream_t st) {
 }
 
 std::unique_ptr<zk_pk_dev> pk_create(zk_ctx* ctx, const zk_r1cs_csr* q, uint64_t num_public, uint32_t shard,
-                                     uint32_t nshards) {
+                                     uint32_t nshards, bool sound) {
+  if (sound && nshards != 1) throw Error(ZK_ERR_ARG, "a sound proving key cannot be sharded");
   std::unique_ptr<zk_pk_dev> d(new zk_pk_dev());
   d->device = ctx->device;
+  d->scalar_bits = sound ? 255 : 64;
   d->V = q->num_variables;
   d->nc = q->num_constraints;
   if (d->nc > (1ull << 32)) throw Error(ZK_ERR_DOMAIN, "more than 2^32 constraints (Fr 2-adicity 32)");
@@ -88,9 +90,16 @@ static void pow64_chain(const host::X<typename C::HF>& P, ABI* out) {
 }
 
 KeyExtras key_extras(uint32_t shard, const zk_g1_affine& alpha_g1, const zk_g1_affine& beta_g1,
-                     const zk_g1_affine& delta_g1, const zk_g2_affine& beta_g2, const zk_g2_affine& delta_g2) {
+                     const zk_g1_affine& delta_g1, const zk_g2_affine& beta_g2, const zk_g2_affine& delta_g2,
+                     bool sound) {
   KeyExtras ex;
   if (shard != 0) return ex;
+  if (sound) {   // whole scalars: 1 alpha_1 + r delta_1, 1 beta_2 + s delta_2, 1 beta_1
+    ex.a = {alpha_g1, delta_g1};
+    ex.b2 = {beta_g2, delta_g2};
+    ex.b1 = {beta_g1};
+    return ex;
+  }
   ex.a.resize(5);
   ex.a[0] = alpha_g1;
   pow64_chain<G1>(host::x_from_abi(delta_g1), &ex.a[1]);
@@ -158,10 +167,11 @@ static void upload_slot(zk_pk_dev& d, const SlotShape& sh, const ABI* v, const s
   });
 }
 
-zk_pk_dev* pk_upload(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs_csr* q, uint32_t shard, uint32_t nshards) {
+zk_pk_dev* pk_upload(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs_csr* q, uint32_t shard, uint32_t nshards,
+                     bool sound) {
   hipStream_t st = ctx->stream;
-  std::unique_ptr<zk_pk_dev> d = pk_create(ctx, q, pk->num_public, shard, nshards);
-  const KeyExtras ex = key_extras(shard, pk->alpha_g1, pk->beta_g1, pk->delta_g1, pk->beta_g2, pk->delta_g2);
+  std::unique_ptr<zk_pk_dev> d = pk_create(ctx, q, pk->num_public, shard, nshards, sound);
+  const KeyExtras ex = key_extras(shard, pk->alpha_g1, pk->beta_g1, pk->delta_g1, pk->beta_g2, pk->delta_g2, sound);
   const uint64_t V = d->V, first_private = pk->num_public + 1;
   const std::vector<uint8_t> own = var_owner(q, d->n, nshards);
   // the a/b vectors may be shorter than V (core:171 `i < pk.a_g1.len()`): indices stay < V.
@@ -314,13 +324,25 @@ static int prove_win_c(const zk_ctx* ctx, const zk_pk_dev& pk) {
   return pk.n / std::max<uint64_t>(pk.nshards, 1) >= (1ull << 24) ? 22 : 16;
 }
 
+// A sound key's MSMs take whole 255-bit scalars: ceil(255 / c) shifted copies,
+// 16 at c = 16 (2^15 buckets per MSM), 13 at c = 20 (2^19), 12 at c = 22
+// (2^21).  The sweep behind the default is in DESIGN.md 2.12.
+// zk_ctx_set_option(ZK_OPT_SOUND_WIN_C) forces 16, 20 or 22.
+constexpr int SOUND_WIN_C_DEFAULT = 20;
+static int sound_win_c(const zk_ctx* ctx) { return ctx->sound_win_c ? ctx->sound_win_c : SOUND_WIN_C_DEFAULT; }
+
 static void pk_precompute_windows(zk_ctx* ctx, zk_pk_dev& pk) {
-  const int PROVE_WIN_C = prove_win_c(ctx, pk), PROVE_WIN = (64 + PROVE_WIN_C - 1) / PROVE_WIN_C;
+  const int PROVE_WIN_C = pk.sound() ? sound_win_c(ctx) : prove_win_c(ctx, pk);
+  const int PROVE_WIN = ((int)pk.scalar_bits + PROVE_WIN_C - 1) / PROVE_WIN_C;
   hipStream_t st = ctx->stream;
   for (int slot = 0; slot < NUM_MSM; slot++) {
     if (slot == MSM_IC) continue;   // windowed together with H (zk_pk_dev::ich_tot)
     const size_t n = slot == MSM_H ? pk.ich_tot() : (size_t)pk.count[slot] + pk.extras[slot];
     const size_t asz = slot == MSM_B2 ? sizeof(G2A) : sizeof(G1A);
+    // every (point, window) entry of an MSM is a 31-bit index (msm.hip)
+    if ((uint64_t)n * PROVE_WIN >= MSM_DUMMY)
+      throw Error(ZK_ERR_ARG, "proving key: " + std::to_string(n) + " bases x " + std::to_string(PROVE_WIN) +
+                                  " window copies exceed the 2^31 window bases of one MSM");
     DevBuf big;
     big.ensure(asz * std::max<size_t>(n * PROVE_WIN, 1));
     if (slot == MSM_H) {   // [IC | H]

@@ -47,6 +47,25 @@ static __device__ __noinline__ XYZZ<FqC> pr_g1_mul64(const Affine<FqC>* P, uint6
   }
   return t;
 }
+// k P for a whole scalar k < r (sound mode): k = 4 u64 limbs in device memory,
+// 255 bits from the top, the same rolled double-and-add
+static __device__ __noinline__ XYZZ<FqC> pr_g1_mul255(const Affine<FqC>* P, const uint64_t* k) {
+  XYZZ<FqC> t;
+  xyzz_set_inf(t);
+#pragma unroll 1
+  for (int b = 254; b >= 0; b--) {
+    t = xyzz_dbl(t);
+    if ((k[b >> 6] >> (b & 63)) & 1) t = xyzz_madd(t, *P);
+  }
+  return t;
+}
+// a 4-limb public input is a reduced Fr (< r)
+static __device__ __forceinline__ bool pr_fr_reduced(const uint64_t* k) {
+#pragma unroll
+  for (int i = 3; i >= 0; i--)
+    if (k[i] != FR_MOD64[i]) return k[i] < FR_MOD64[i];
+  return false;
+}
 // x = X / ZZ, y = Y / ZZZ with one inversion: 1 / ZZ = (ZZ / ZZZ)^2
 ZK_DI Affine<FqC> pr_g1_affine(const XYZZ<FqC>& p) {
   const FqC i3 = {pr_fq_inv(p.ZZZ.v)};
@@ -55,7 +74,10 @@ ZK_DI Affine<FqC> pr_g1_affine(const XYZZ<FqC>& p) {
 }
 
 // One lane per proof: Verifier::verify (verify.hip's zk_groth16_verify) with
-// the four Miller loops sharing their squarings.
+// the four Miller loops sharing their squarings.  SOUND
+// (zk_groth16_verify_sound): every x_k whole -- one >= r makes the proof
+// MALFORMED -- instead of its lo64.
+template <bool SOUND>
 __global__ void __launch_bounds__(PR_BLOCK) k_groth16_verify(const uint64_t* __restrict__ proofs,
                                                              const uint64_t* __restrict__ inputs, size_t n_inputs,
                                                              const uint32_t* __restrict__ vk, size_t n,
@@ -69,22 +91,28 @@ __global__ void __launch_bounds__(PR_BLOCK) k_groth16_verify(const uint64_t* __r
   bool ok = pr_load_g1(w, &A, &a_inf);
   ok = pr_load_g2(w + G1W, &in.Q, &b_inf) && ok;
   ok = pr_load_g1(w + G1W + G2W, &Cp, &c_inf) && ok;
+  if constexpr (SOUND) {
+#pragma unroll 1
+    for (size_t k = 0; k < n_inputs; k++) ok = ok && pr_fr_reduced(inputs + 4 * (n_inputs * i + k));
+  }
   if (!ok) {
     status[i] = ZK_VERIFY_MALFORMED;
     return;
   }
-  // IC = ic[0] + sum lo64(x_k) ic[k + 1] over the non-zero lo64(x_k)
+  // IC = ic[0] + sum lo64(x_k) ic[k + 1] over the non-zero lo64(x_k)  (SOUND: the whole x_k)
   Affine<FqC> ic;
   ic.x = {pr_fq_load(vk + VK_IC)};
   ic.y = {pr_fq_load(vk + VK_IC + 12)};
   XYZZ<FqC> acc = xyzz_from_aff(ic);
 #pragma unroll 1
   for (size_t k = 0; k < n_inputs; k++) {
-    const uint64_t x = inputs[4 * (n_inputs * i + k)];
+    const uint64_t* xw = inputs + 4 * (n_inputs * i + k);
+    const uint64_t x = SOUND ? (xw[0] | xw[1] | xw[2] | xw[3]) : xw[0];
     ic.x = {pr_fq_load(vk + VK_IC + 24 * (k + 1))};
     ic.y = {pr_fq_load(vk + VK_IC + 24 * (k + 1) + 12)};
     if (!x || aff_is_inf(ic)) continue;
-    acc = xyzz_add(acc, pr_g1_mul64(&ic, x));
+    if constexpr (SOUND) acc = xyzz_add(acc, pr_g1_mul255(&ic, xw));
+    else acc = xyzz_add(acc, pr_g1_mul64(&ic, x));
   }
   const bool ic_inf = xyzz_is_inf(acc);
   if (!ic_inf) ic = pr_g1_affine(acc);
@@ -203,7 +231,7 @@ static bool pairing_tables(const zk_vk& vk, size_t n_inputs, std::vector<uint32_
 // As points_run: the batch crosses the GPU in chunks of ctx->verify_chunk
 // proofs (products) on the ctx's main stream; buffers belong to the call.
 static int verify_many_run(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs, const zk_fr* inputs, size_t n_inputs,
-                           size_t n, uint8_t* status) {
+                           size_t n, uint8_t* status, bool sound) {
   if (n_inputs != vk->num_public) return ZK_ERR_INVALID_WITNESS;
   if (!vk->ic_g1 || vk->ic_len < n_inputs + 1) {
     ctx->err = "verification key: ic_g1 shorter than the public inputs";
@@ -228,8 +256,12 @@ static int verify_many_run(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs,
     ZK_HIP(hipMemcpyAsync(d_proofs.p, proofs + lo, sizeof(zk_proof) * m, hipMemcpyHostToDevice, st));
     if (in_sz) ZK_HIP(hipMemcpyAsync(d_in.p, inputs + n_inputs * lo, in_sz * m, hipMemcpyHostToDevice, st));
     const int pi = ctx->prof.begin(st, "verify", m);
-    k_groth16_verify<<<ceil_div(m, PR_BLOCK), PR_BLOCK, 0, st>>>(d_proofs.as<uint64_t>(), d_in.as<uint64_t>(), n_inputs,
-                                                                 d_vk.as<uint32_t>(), m, d_st.as<uint8_t>());
+    if (sound)
+      k_groth16_verify<true><<<ceil_div(m, PR_BLOCK), PR_BLOCK, 0, st>>>(
+          d_proofs.as<uint64_t>(), d_in.as<uint64_t>(), n_inputs, d_vk.as<uint32_t>(), m, d_st.as<uint8_t>());
+    else
+      k_groth16_verify<false><<<ceil_div(m, PR_BLOCK), PR_BLOCK, 0, st>>>(
+          d_proofs.as<uint64_t>(), d_in.as<uint64_t>(), n_inputs, d_vk.as<uint32_t>(), m, d_st.as<uint8_t>());
     ZK_LAUNCH_CHECK();
     ctx->prof.end(st, pi);
     ZK_HIP(hipMemcpyAsync(status + lo, d_st.p, m, hipMemcpyDeviceToHost, st));
@@ -285,7 +317,12 @@ using namespace zk;
 int zk_groth16_verify_many(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs, const zk_fr* public_inputs,
                            size_t n_inputs, size_t n_proofs, uint8_t* status) {
   if (!ctx || !vk || (n_proofs && (!proofs || !status || (n_inputs && !public_inputs)))) return ZK_ERR_ARG;
-  ZK_PGUARD(ctx, { return verify_many_run(ctx, vk, proofs, public_inputs, n_inputs, n_proofs, status); })
+  ZK_PGUARD(ctx, { return verify_many_run(ctx, vk, proofs, public_inputs, n_inputs, n_proofs, status, false); })
+}
+int zk_groth16_verify_many_sound(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs, const zk_fr* public_inputs,
+                                 size_t n_inputs, size_t n_proofs, uint8_t* status) {
+  if (!ctx || !vk || (n_proofs && (!proofs || !status || (n_inputs && !public_inputs)))) return ZK_ERR_ARG;
+  ZK_PGUARD(ctx, { return verify_many_run(ctx, vk, proofs, public_inputs, n_inputs, n_proofs, status, true); })
 }
 int zk_pairing_products(zk_ctx* ctx, const zk_g1_affine* g1, const zk_g2_affine* g2, size_t pairs_per_product,
                         size_t n_products, uint8_t* status) {

@@ -106,6 +106,33 @@ __global__ void k_set_extras(uint64_t* __restrict__ dst, Extras e, uint32_t n) {
   if (threadIdx.x < n) dst[threadIdx.x] = e.v[threadIdx.x];
 }
 
+// ---- a sound key (zk_pk_dev::sound): the same scalars whole, 4 words each ----
+// k_h_final / k_h_lo64 without the truncation: canonical H_i
+__global__ void __launch_bounds__(256) k_h_final_full(const Fr* __restrict__ hb, const Fr* __restrict__ gipow,
+                                                      uint32_t log_n, Fr* __restrict__ h) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >> log_n) return;
+  st_vec(&h[i], fp_from_mont(fp_mul(ld_vec(&hb[brev((uint32_t)i, log_n)]), ld_vec(&gipow[i]))));
+}
+__global__ void __launch_bounds__(256) k_h_canon(const Fr* __restrict__ h, size_t n, Fr* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  st_vec(&out[i], fp_from_mont(ld_vec(&h[i])));
+}
+// out[k] = src[idx[k]], whole canonical Fr
+__global__ void __launch_bounds__(256) k_gather_fr(const Fr* __restrict__ src, const uint32_t* __restrict__ idx,
+                                                   uint32_t count, Fr* __restrict__ out) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  st_vec(&out[k], ld_vec(&src[idx[k]]));
+}
+struct ExtrasFr {
+  uint64_t v[8];   // two whole scalars: 1, then r or s
+};
+__global__ void k_set_extras_fr(uint64_t* __restrict__ dst, ExtrasFr e, uint32_t nwords) {
+  if (threadIdx.x < nwords) dst[threadIdx.x] = e.v[threadIdx.x];
+}
+
 // flags bit 3: some z_i >= r.  The reference's assignment is a vector of
 // reduced Fr (core:40-44), so a non-canonical limb vector has no reference
 // meaning (its lo64 would differ from the reduced value's): ZK_ERR_ARG.
@@ -140,8 +167,11 @@ struct Partial {
 };
 static_assert(sizeof(Partial) <= ZK_PARTIAL_BYTES, "partial size");
 
+// h_out: lo64(H_i), one word per coefficient; for a sound key the whole
+// canonical H_i, four words each
 static void quotient(zk_ctx* ctx, const zk_pk_dev* pk, const uint64_t* d_z, hipStream_t st, uint64_t* h_out) {
   const uint64_t n = pk->n;
+  const bool full = pk->sound();
   NttDomain& dom = ctx->domain(pk->log_n);
   ctx->qabc.ensure(sizeof(Fr) * 3 * n);
   Fr* v[3] = {ctx->qabc.as<Fr>(), ctx->qabc.as<Fr>() + n, ctx->qabc.as<Fr>() + 2 * n};
@@ -185,11 +215,15 @@ static void quotient(zk_ctx* ctx, const zk_pk_dev* pk, const uint64_t* d_z, hipS
   // natural order (the bit reversal is the first pass's tiled gather,
   // n^-1 g^-i fused into the last pass's store) into v[1], v[2] as scratch,
   // since beyond the MALL every gathered 32-B element was its own line/page
-  ctx->tmp_scal.ensure(sizeof(uint64_t) * n);
+  ctx->tmp_scal.ensure(sizeof(uint64_t) * (full ? 4 : 1) * n);
   if (!large) {
     ntt_dif(v[0], dom, true, st, pf);
     ph = pf->begin(st, "quotient_misc", n);
-    k_h_final<<<ceil_div(n, 256), 256, 0, st>>>(v[0], domain_gipow(dom, st), pk->log_n, h_out);
+    if (full)
+      k_h_final_full<<<ceil_div(n, 256), 256, 0, st>>>(v[0], domain_gipow(dom, st), pk->log_n,
+                                                       reinterpret_cast<Fr*>(h_out));
+    else
+      k_h_final<<<ceil_div(n, 256), 256, 0, st>>>(v[0], domain_gipow(dom, st), pk->log_n, h_out);
     ZK_LAUNCH_CHECK();
     pf->end(st, ph);
     return;
@@ -202,7 +236,8 @@ static void quotient(zk_ctx* ctx, const zk_pk_dev* pk, const uint64_t* d_z, hipS
     ntt_natural(v[1], v[0], v[2], dom, true, st, pf, nullptr, domain_gipow(dom, st), nullptr);
   }
   ph = pf->begin(st, "quotient_misc", n);
-  k_h_lo64<<<ceil_div(n, 256), 256, 0, st>>>(h, n, h_out);
+  if (full) k_h_canon<<<ceil_div(n, 256), 256, 0, st>>>(h, n, reinterpret_cast<Fr*>(h_out));
+  else k_h_lo64<<<ceil_div(n, 256), 256, 0, st>>>(h, n, h_out);
   ZK_LAUNCH_CHECK();
   pf->end(st, ph);
 }
@@ -286,6 +321,12 @@ struct ProveRun {
   // accumulation of another.  Schedule 3 runs everything in order on main.
   const bool serial;
   const hipStream_t s_g2, s_abi;
+  // A sound key: every scalar whole (sw = 4 words, 255 bits) instead of its
+  // lo64, over the key's ceil(255 / c) window copies, and A, B1 and IC+H each
+  // an MSM of its own (msm_launch_shared) on the same streams; the witness is
+  // whole on the device before the first kernel (no split upload).
+  const bool sound;
+  const int sw, bits;
   // The quotient: local (every coefficient), distributed over the ranks of
   // a sharded key (this rank's coefficients i = shard mod N), or given
   // (virtual-rank tests).
@@ -305,7 +346,7 @@ struct ProveRun {
   ProveRun(zk_ctx* c, const zk_pk_dev* k, const zk_fr* r_, const zk_fr* s_, const ProveInput& i)
       : ctx(c), pk(k), r(r_), s(s_), in(i), st(c->stream), split(i.z_host != nullptr), serial(c->sched == 3),
         s_g2(serial ? st : c->side[0]), s_abi(serial ? st : c->side[1]),
-        dist(!i.h_given && uses_dist_quotient(c, k)),
+        sound(k->sound()), sw(k->sound() ? 4 : 1), bits((int)k->scalar_bits),        dist(!i.h_given && uses_dist_quotient(c, k)),
         h_src(i.h_given ? i.h_given : c->tmp_scal.as<uint64_t>()), h_div((i.h_given || dist) ? k->nshards : 1),
         nic(k->count[MSM_IC]), h_direct(k->h_ident && !dist && !i.h_given) {}
 
@@ -343,17 +384,30 @@ struct ProveRun {
   void set_extras(int slot, hipStream_t ss) {
     const uint32_t nex = pk->extras[slot];
     if (!nex) return;
+    const zk_fr* whole = slot == MSM_A ? r : slot == MSM_B2 ? s : nullptr;
+    if (sound) {   // 1 for alpha_1 / beta_2 / beta_1, then r (delta_1) or s (delta_2) whole
+      ExtrasFr ex{};
+      ex.v[0] = 1;
+      if (whole) for (int k = 0; k < 4; k++) ex.v[4 + k] = whole->l[k];
+      k_set_extras_fr<<<1, 64, 0, ss>>>(scal(slot) + 4 * (size_t)pk->count[slot], ex, 4 * nex);
+      ZK_LAUNCH_CHECK();
+      return;
+    }
     Extras ex{};
     ex.v[0] = 1;
-    const zk_fr* full = slot == MSM_A ? r : slot == MSM_B2 ? s : nullptr;
-    if (full) for (int k = 0; k < 4; k++) ex.v[1 + k] = full->l[k];
+    if (whole) for (int k = 0; k < 4; k++) ex.v[1 + k] = whole->l[k];
     k_set_extras<<<1, 64, 0, ss>>>(scal(slot) + pk->count[slot], ex, nex);
     ZK_LAUNCH_CHECK();
   }
   // lo64(z) behind compacted positions [lo, hi) of an A / B2 / B1 slot ([0, count): all), and the extras
   void gather(int slot, uint32_t lo, uint32_t hi, bool extras, hipStream_t ss) {
-    ctx->scal[slot].ensure(sizeof(uint64_t) * std::max<uint32_t>(pk->count[slot] + pk->extras[slot], 1));
-    if (hi > lo) {
+    ctx->scal[slot].ensure(sizeof(uint64_t) * sw * std::max<uint32_t>(pk->count[slot] + pk->extras[slot], 1));
+    if (hi > lo && sound) {
+      k_gather_fr<<<ceil_div(hi - lo, 256), 256, 0, ss>>>(reinterpret_cast<const Fr*>(in.d_z),
+                                                         pk->idx[slot].as<uint32_t>() + lo, hi - lo,
+                                                         reinterpret_cast<Fr*>(scal(slot)) + lo);
+      ZK_LAUNCH_CHECK();
+    } else if (hi > lo) {
       k_gather_lo64<<<ceil_div(hi - lo, 256), 256, 0, ss>>>(in.d_z, 4, pk->idx[slot].as<uint32_t>() + lo, 1u, hi - lo,
                                                            scal(slot) + lo);
       ZK_LAUNCH_CHECK();
@@ -362,7 +416,12 @@ struct ProveRun {
   }
   void gather_ic(hipStream_t ss) {
     if (!nic) return;
-    k_gather_lo64<<<ceil_div(nic, 256), 256, 0, ss>>>(in.d_z, 4, pk->idx[MSM_IC].as<uint32_t>(), 1u, nic, scal(MSM_H));
+    if (sound)
+      k_gather_fr<<<ceil_div(nic, 256), 256, 0, ss>>>(reinterpret_cast<const Fr*>(in.d_z),
+                                                     pk->idx[MSM_IC].as<uint32_t>(), nic,
+                                                     reinterpret_cast<Fr*>(scal(MSM_H)));
+    else
+      k_gather_lo64<<<ceil_div(nic, 256), 256, 0, ss>>>(in.d_z, 4, pk->idx[MSM_IC].as<uint32_t>(), 1u, nic, scal(MSM_H));
     ZK_LAUNCH_CHECK();
   }
   void gather_ic_early() {
@@ -373,11 +432,26 @@ struct ProveRun {
   void gather_ich(hipStream_t ss) {
     if (!ic_ready) gather_ic(ss);
     const uint32_t cnt = pk->count[MSM_H];
-    if (cnt && !h_direct) {
+    if (cnt && !h_direct && sound) {   // never sharded: h_div = 1
+      k_gather_fr<<<ceil_div(cnt, 256), 256, 0, ss>>>(reinterpret_cast<const Fr*>(h_src),
+                                                     pk->idx[MSM_H].as<uint32_t>(), cnt,
+                                                     reinterpret_cast<Fr*>(scal(MSM_H)) + nic);
+      ZK_LAUNCH_CHECK();
+    } else if (cnt && !h_direct) {
       k_gather_lo64<<<ceil_div(cnt, 256), 256, 0, ss>>>(h_src, 1, pk->idx[MSM_H].as<uint32_t>(), h_div, cnt,
                                                         scal(MSM_H) + nic);
       ZK_LAUNCH_CHECK();
     }
+  }
+  // One MSM of a sound key over the slot's window copies (MSM_H: [IC | H]), downloaded
+  template <class C>
+  void launch_shared(int slot, const char* tag, hipStream_t gs) {
+    MsmWork& w = ctx->msm[slot];
+    w.tag = serial ? tag : "";
+    const uint32_t n = slot == MSM_H ? pk->ich_tot() : pk->count[slot] + pk->extras[slot];
+    msm_launch_shared<C>(w, pk->bases[slot].as<typename C::A>(), scal(slot), sw, n, bits, pk->win_c, gs,
+                         pk->stride[slot]);
+    msm_download<C>(w, gs);
   }
   // n points from compacted position lo of a slot's window-shifted bases (MSM_H: the [IC | H] vector)
   MsmSeg seg(int slot, uint32_t lo, uint32_t n) const {
@@ -455,8 +529,8 @@ struct ProveRun {
       MsmWork& w = ctx->msm[MSM_B2];
       w.tag = serial ? "B2/" : "";
       gather(MSM_B2, 0, pk->count[MSM_B2], true, s_g2);
-      msm_launch_shared<G2>(w, pk->bases[MSM_B2].as<G2A>(), scal(MSM_B2), 1, pk->count[MSM_B2] + pk->extras[MSM_B2], 64,
-                            pk->win_c, s_g2, pk->stride[MSM_B2]);
+      msm_launch_shared<G2>(w, pk->bases[MSM_B2].as<G2A>(), scal(MSM_B2), sw, pk->count[MSM_B2] + pk->extras[MSM_B2],
+                            bits, pk->win_c, s_g2, pk->stride[MSM_B2]);
       msm_download<G2>(w, s_g2);
       ZK_HIP(hipEventRecord(ctx->ev_done[MSM_B2], s_g2));
     }
@@ -464,7 +538,19 @@ struct ProveRun {
       ZK_HIP(hipStreamWaitEvent(s_abi, ctx->ev_scal, 0));
       gather_ic_early();
     }
-    launch_batch(G1_AB, 2, "AB/", s_abi);
+    if (!sound) {
+      launch_batch(G1_AB, 2, "AB/", s_abi);
+      return;
+    }
+    // whole scalars: A, then B1, each its own MSM (msm_front_impl batches
+    // one-word scalars only: the two as one batch at sw = 4 measured slower in
+    // the overlapped prove); ev_done[MSM_A] still stands for both
+    Range range("msm_g1_a_b1");
+    gather(MSM_A, 0, pk->count[MSM_A], true, s_abi);
+    launch_shared<G1>(MSM_A, "A/", s_abi);
+    gather(MSM_B1, 0, pk->count[MSM_B1], true, s_abi);
+    launch_shared<G1>(MSM_B1, "B1/", s_abi);
+    ZK_HIP(hipEventRecord(ctx->ev_done[MSM_A], s_abi));
   }
 
   // ---- the quotient, then IC + H on the main stream
@@ -477,8 +563,8 @@ struct ProveRun {
     } else {
       // (Az, Bz, Cz) -> lo64(H): in place in the IC+H scalars, else in
       // tmp_scal (sized here, before its pointer is taken)
-      ctx->tmp_scal.ensure(sizeof(uint64_t) * pk->n);
-      quotient(ctx, pk, in.d_z, st, h_direct ? scal(MSM_H) + nic : ctx->tmp_scal.as<uint64_t>());
+      ctx->tmp_scal.ensure(sizeof(uint64_t) * sw * pk->n);
+      quotient(ctx, pk, in.d_z, st, h_direct ? scal(MSM_H) + (size_t)sw * nic : ctx->tmp_scal.as<uint64_t>());
     }
     h_src = ctx->tmp_scal.as<uint64_t>();
   }
@@ -486,7 +572,8 @@ struct ProveRun {
   void launch() {
     // the IC+H scalar vector, sized once before any stream writes it (IC's
     // gather on the A+B1 stream, H's lo64 from the quotient when h_direct)
-    ctx->scal[MSM_H].ensure(sizeof(uint64_t) * std::max<uint64_t>({(uint64_t)pk->ich_tot(), (uint64_t)nic + pk->n, 1}));
+    ctx->scal[MSM_H].ensure(sizeof(uint64_t) * sw *
+                            std::max<uint64_t>({(uint64_t)pk->ich_tot(), (uint64_t)nic + pk->n, 1}));
     // MSMs first, then the quotient (enqueueing the quotient first measured
     // 0.37 ms slower: profiles/r03_ab_quotient_first_rejected.txt).  With
     // ZK_OPT_EXCHANGE_FIRST a distributed quotient goes first and the side
@@ -514,7 +601,14 @@ struct ProveRun {
     flags_agreed = dist && ctx->exch->agree_max_dev(flags(), st);
     ZK_HIP(hipMemcpyAsync(ctx->flags_host.p, ctx->flags.p, 4, hipMemcpyDeviceToHost, st));
     if (ic_ready) ZK_HIP(hipStreamWaitEvent(st, ctx->ev_ic, 0));
-    launch_batch(G1_ICH, 1, "ICH/", st);
+    if (sound) {
+      Range range("msm_g1_ic_h");
+      gather_ich(st);
+      launch_shared<G1>(MSM_H, "ICH/", st);
+      ZK_HIP(hipEventRecord(ctx->ev_done[MSM_H], st));
+    } else {
+      launch_batch(G1_ICH, 1, "ICH/", st);
+    }
     if (ph_span >= 0) {
       for (int sl : WAITS) ZK_HIP(hipStreamWaitEvent(st, ctx->ev_done[sl], 0));
       ctx->prof.end(st, ph_span);
@@ -546,11 +640,11 @@ struct ProveRun {
           p.B2 = msm_finish<G2>(ctx->msm[slot]);
           if (in.early) host_to_abi<G2>(p.B2, reinterpret_cast<uint64_t*>(&in.early->b));
         } else if (slot == MSM_A) {
-          p.A = msm_finish_seg<G1>(ctx->msm[slot], 0);
-          p.B1 = msm_finish_seg<G1>(ctx->msm[slot], 1);
+          p.A = sound ? msm_finish<G1>(ctx->msm[MSM_A]) : msm_finish_seg<G1>(ctx->msm[slot], 0);
+          p.B1 = sound ? msm_finish<G1>(ctx->msm[MSM_B1]) : msm_finish_seg<G1>(ctx->msm[slot], 1);
           ab_done = true;
         } else {
-          p.IC = msm_finish_seg<G1>(ctx->msm[slot], 0);   // IC + H_1
+          p.IC = sound ? msm_finish<G1>(ctx->msm[slot]) : msm_finish_seg<G1>(ctx->msm[slot], 0);   // IC + H_1
           p.H = host::inf<host::Fq>();
         }
         done[wi] = progressed = true;
@@ -626,6 +720,12 @@ int prove_impl(zk_ctx* ctx, const zk_pk_dev* pk, const void* d_z, size_t zlen, s
   ProveInput in{reinterpret_cast<const uint64_t*>(d_z)};
   in.early = &ab;
   in.z_host = z_host;
+  if (pk->sound() && z_host) {
+    // a sound key's host witness goes up whole, then takes the device path
+    // (the split, overlapped upload is the 64-bit schedule's)
+    ZK_HIP(hipMemcpyAsync(const_cast<void*>(d_z), z_host, sizeof(zk_fr) * zlen, hipMemcpyHostToDevice, ctx->stream));
+    in.z_host = nullptr;
+  }
   Partial p = prove_partial(ctx, pk, r, s, in);
   if (p.status != ZK_OK) return p.status;
   // combine() for one part: pi_A, pi_B already converted; pi_C = IC + H + s A + r B1
@@ -659,6 +759,10 @@ static int prove_partial_common(zk_ctx* ctx, const zk_pk_dev* pk, const void* d_
                                 const std::vector<uint64_t>* ranges, size_t zlen, size_t num_public,
                                 const zk_fr* r, const zk_fr* s, zk_prove_partial* out, bool bad_slice = false) {
   std::memset(out, 0, sizeof *out);
+  if (pk->sound()) {
+    ctx->err = "a sound proving key is never sharded: use zk_groth16_prove / zk_groth16_prove_dev";
+    return ZK_ERR_ARG;
+  }
   Partial p{};
   int local = ZK_OK;
   if (bad_slice || !fr_canonical(*r) || !fr_canonical(*s)) local = ZK_ERR_ARG;

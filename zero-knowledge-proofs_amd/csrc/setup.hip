@@ -27,7 +27,10 @@
 namespace zk {
 
 // ---------------------------------------------------- fixed-base tables ---
-// T[w][d] = d * 2^(8w) * G, w < 8, d < 256 (affine, Montgomery); T[w][0] unused.
+// T[w][d] = d * 2^(8w) * G, w < W, d < 256 (affine, Montgomery); T[w][0] unused.
+// W = 8 byte windows for the reference's 64-bit scalars, 32 for the whole
+// scalars of a sound setup (8 160 entries: 0.8 MB for G1, 1.6 MB for G2).
+constexpr int FB_WIN64 = 8, FB_WIN255 = 32;
 template <class C>
 struct FbTable {
   std::vector<typename C::A> host;
@@ -50,17 +53,17 @@ static host::X<host::Fq2> g2_gen_host() {
 }
 
 template <class HF, class DA>
-static void build_table(const host::X<HF>& G, std::vector<DA>& out) {
+static void build_table(const host::X<HF>& G, int W, std::vector<DA>& out) {
   using HX = host::X<HF>;
-  std::vector<HX> pts(2048);
+  std::vector<HX> pts(W * 256);
   HX base = G;
-  for (int w = 0; w < 8; w++) {
+  for (int w = 0; w < W; w++) {
     pts[w * 256] = host::inf<HF>();
     for (int d = 1; d < 256; d++) pts[w * 256 + d] = host::addp(pts[w * 256 + d - 1], base);
     for (int k = 0; k < 8; k++) base = host::dbl(base);
   }
-  out.resize(2048);
-  for (int i = 0; i < 2048; i++) {
+  out.resize(W * 256);
+  for (int i = 0; i < W * 256; i++) {
     HF x, y;
     if (!host::to_affine(pts[i], x, y)) { x = host::f_zero<HF>(); y = host::f_zero<HF>(); }
     x = host::to_dev(x);   // device Montgomery radix (constants.hpp)
@@ -155,6 +158,21 @@ __global__ void __launch_bounds__(256) k_lo64(const Fr* __restrict__ in, size_t 
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = lo64_of(ld_vec(&in[i]));
 }
+// Sound setup: the same scalars whole, as canonical 4-limb Fr (k holds the
+// full-width alpha, beta, delta^-1, gamma^-1); nothing is truncated.
+__global__ void __launch_bounds__(256) k_setup_scalars_full(const Fr* __restrict__ av, const Fr* __restrict__ bv,
+                                                            const Fr* __restrict__ cv, SetupConsts k,
+                                                            Fr* __restrict__ sa, Fr* __restrict__ sb,
+                                                            Fr* __restrict__ sic, Fr* __restrict__ svk) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= k.V) return;
+  const Fr a = ld_vec(&av[i]), b = ld_vec(&bv[i]), c = ld_vec(&cv[i]);
+  st_vec(&sa[i], fp_from_mont(a));
+  st_vec(&sb[i], fp_from_mont(b));
+  const Fr t = fp_add(fp_add(fp_mul(k.be, a), fp_mul(k.al, b)), c);
+  if (i > k.num_public) st_vec(&sic[i - k.num_public - 1], fp_from_mont(fp_mul(t, k.dinv)));
+  else st_vec(&svk[i], fp_from_mont(fp_mul(t, k.ginv)));
+}
 
 // XYZZ = sum_w T[w][byte_w(k)]  (<= 8 mixed additions), k = scal[idx ? idx[i] : i]
 template <class C>
@@ -169,6 +187,31 @@ __global__ void __launch_bounds__(128) k_fixed_base(const typename C::A* __restr
   xyzz_set_inf(acc);
   for (int w = 0; w < 8; w++) {
     const uint32_t d = (uint32_t)(k >> (8 * w)) & 255u;
+    if (d) acc = xyzz_madd(acc, ld_vec(&T[w * 256 + d]));
+  }
+  st_vec(&out[i], acc);
+}
+// The same for a whole canonical scalar k < r of 4 u64 limbs (sound setup):
+// XYZZ = sum_w T[w][byte_w(k)] over 32 byte windows, <= 32 mixed additions.
+// The partial sum before window w is (k mod 2^(8w)) G, below every entry
+// d 2^(8w) G of that window and the total below r G: never the doubling or the
+// cancelling case of the mixed addition.  The loop stays rolled and reads the
+// scalar a byte at a time (its little-endian bytes are the windows): beside
+// the accumulator only a pointer and a counter live across an addition, which
+// the G2 variant at 256 VGPRs needs.
+template <class C>
+__global__ void __launch_bounds__(128) k_fixed_base_wide(const typename C::A* __restrict__ T,
+                                                         const uint64_t* __restrict__ scal,
+                                                         const uint32_t* __restrict__ idx, size_t n,
+                                                         typename C::X* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* k = reinterpret_cast<const uint8_t*>(scal + 4 * (size_t)(idx ? idx[i] : i));
+  typename C::X acc;
+  xyzz_set_inf(acc);
+#pragma unroll 1
+  for (int w = 0; w < FB_WIN255; w++) {
+    const uint32_t d = k[w];
     if (d) acc = xyzz_madd(acc, ld_vec(&T[w * 256 + d]));
   }
   st_vec(&out[i], acc);
@@ -214,31 +257,36 @@ __global__ void __launch_bounds__(256) k_to_abi_g2(const G2A* __restrict__ in, s
 // ------------------------------------------------------------- helpers ---
 static std::mutex g_tab_mu;
 template <class C>
-static FbTable<C>& fb_table(int device, hipStream_t st) {
-  static std::map<int, FbTable<C>> tabs;   // one per group
+static FbTable<C>& fb_table(int device, int W, hipStream_t st) {
+  static std::map<std::pair<int, int>, FbTable<C>> tabs;   // one per group, device and window count
   std::lock_guard<std::mutex> lk(g_tab_mu);
-  FbTable<C>& t = tabs[device];
+  FbTable<C>& t = tabs[{device, W}];
   if (t.host.empty()) {
-    if constexpr (C::ABI_WORDS == 13) build_table(g1_gen_host(), t.host);
-    else build_table(g2_gen_host(), t.host);
-    t.dev.ensure(sizeof(typename C::A) * 2048);
-    ZK_HIP(hipMemcpyAsync(t.dev.p, t.host.data(), sizeof(typename C::A) * 2048, hipMemcpyHostToDevice, st));
+    if constexpr (C::ABI_WORDS == 13) build_table(g1_gen_host(), W, t.host);
+    else build_table(g2_gen_host(), W, t.host);
+    t.dev.ensure(sizeof(typename C::A) * t.host.size());
+    ZK_HIP(hipMemcpyAsync(t.dev.p, t.host.data(), sizeof(typename C::A) * t.host.size(), hipMemcpyHostToDevice, st));
     ZK_HIP(hipStreamSynchronize(st));
   }
   return t;
 }
 
-// out[i] = G * scal[idx ? idx[i] : i], affine Montgomery
+// out[i] = G * scal[idx ? idx[i] : i], affine Montgomery; a scalar is sw u64
+// words: 1 (below 2^64) or 4 (a whole canonical Fr)
 template <class C>
 static void fixed_base(zk_ctx* ctx, const uint64_t* d_scal, const uint32_t* d_idx, size_t n,
-                       typename C::A* d_out, hipStream_t st) {
+                       typename C::A* d_out, hipStream_t st, int sw = 1) {
   if (!n) return;
-  FbTable<C>& T = fb_table<C>(ctx->device, st);
+  FbTable<C>& T = fb_table<C>(ctx->device, sw == 1 ? FB_WIN64 : FB_WIN255, st);
   DevBuf xs, pre;
   xs.ensure(sizeof(typename C::X) * n);
   pre.ensure(sizeof(typename C::F) * n);
-  k_fixed_base<C><<<ceil_div(n, 128), 128, 0, st>>>(T.dev.template as<typename C::A>(), d_scal, d_idx, n,
-                                                     xs.template as<typename C::X>());
+  if (sw == 1)
+    k_fixed_base<C><<<ceil_div(n, 128), 128, 0, st>>>(T.dev.template as<typename C::A>(), d_scal, d_idx, n,
+                                                       xs.template as<typename C::X>());
+  else
+    k_fixed_base_wide<C><<<ceil_div(n, 128), 128, 0, st>>>(T.dev.template as<typename C::A>(), d_scal, d_idx, n,
+                                                            xs.template as<typename C::X>());
   ZK_LAUNCH_CHECK();
   batch_normalize<C>(xs.template as<typename C::X>(), n, pre.template as<typename C::F>(), d_out, st);
   ZK_HIP(hipStreamSynchronize(st));  // xs / pre die here
@@ -272,6 +320,27 @@ void bases_to_abi_host(bool g2, const void* d_in, uint32_t stride, size_t n, uin
   }
   if (g2) to_abi<G2>(static_cast<const G2A*>(src), n, host_out, st);
   else to_abi<G1>(static_cast<const G1A*>(src), n, host_out, st);
+}
+
+// out[i] = G * scalars[i] for n whole canonical scalars through the 255-bit
+// fixed-base kernel, as canonical ABI words in host memory (the test library)
+int fixed_base_wide_host(zk_ctx* ctx, bool g2, const zk_fr* scalars, size_t n, uint64_t* host_out) {
+  for (size_t i = 0; i < n; i++)
+    if (!fr_canonical(scalars[i])) return ZK_ERR_ARG;
+  if (!n) return ZK_OK;
+  hipStream_t st = ctx->stream;
+  DevBuf sc, o;
+  sc.ensure(sizeof(zk_fr) * n);
+  o.ensure((g2 ? sizeof(G2A) : sizeof(G1A)) * n);
+  ZK_HIP(hipMemcpyAsync(sc.p, scalars, sizeof(zk_fr) * n, hipMemcpyHostToDevice, st));
+  if (g2) {
+    fixed_base<G2>(ctx, sc.as<uint64_t>(), nullptr, n, o.as<G2A>(), st, 4);
+    to_abi<G2>(o.as<G2A>(), n, host_out, st);
+  } else {
+    fixed_base<G1>(ctx, sc.as<uint64_t>(), nullptr, n, o.as<G1A>(), st, 4);
+    to_abi<G1>(o.as<G1A>(), n, host_out, st);
+  }
+  return ZK_OK;
 }
 
 // host-side generator multiple by a full-width canonical scalar -> ABI
@@ -336,7 +405,7 @@ static void lagrange_at(const host::Fr& t, uint32_t log_n, DevBuf& wpow, DevBuf&
 
 // ---------------------------------------------------------------- setup ---
 int setup_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_setup_params* P, uint64_t num_public, uint32_t shard,
-               uint32_t nshards, zk_pk* pk_host, zk_pk_dev** pk_dev, zk_vk* vk) {
+               uint32_t nshards, zk_pk* pk_host, zk_pk_dev** pk_dev, zk_vk* vk, bool sound) {
   Range range("zk_setup");
   hipStream_t st = ctx->stream;
   const uint64_t V = q->num_variables, nc = q->num_constraints;
@@ -346,7 +415,7 @@ int setup_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_setup_params* P, uint
   if (num_public >= V) return ZK_ERR_SETUP_PARAMS;
   // truncated copies (setup:155-159); the reference unwraps inverse(d~), inverse(g~)
   const uint64_t al = P->alpha.l[0], be = P->beta.l[0], ga = P->gamma.l[0], de = P->delta.l[0], ta = P->tau.l[0];
-  if (de == 0 || ga == 0) return ZK_ERR_SETUP_PARAMS;
+  if (!sound && (de == 0 || ga == 0)) return ZK_ERR_SETUP_PARAMS;
   if (nc > (1ull << 32)) return ZK_ERR_DOMAIN;
   uint64_t n = 1;
   while (n < nc) n <<= 1;
@@ -354,8 +423,38 @@ int setup_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_setup_params* P, uint
   if (log_n > 32) return ZK_ERR_DOMAIN;
   if (V >= 0x80000000ull || n >= 0x80000000ull) return ZK_ERR_ARG;
 
-  const host::Fr t = host::fr_from_u64(ta);
-  const host::Fr dinv = host::fr_inv(host::fr_from_u64(de)), ginv = host::fr_inv(host::fr_from_u64(ga));
+  // Sound mode (no reference counterpart: the reference truncates) takes every
+  // parameter whole, and h_g1[i] = [tau^i Z(tau) / delta]_1: hk = Z(tau) / delta
+  // scales the tau powers.  tau on the domain gives Z(tau) = 0 and a key whose
+  // H query is all identity: ZK_ERR_SETUP_PARAMS.
+  const int sw = sound ? 4 : 1;   // u64 words per setup scalar
+  host::Fr t, alf, bef, dinv, ginv, hk;
+  if (sound) {
+    if (!fr_canonical(P->alpha) || !fr_canonical(P->beta) || !fr_canonical(P->gamma) || !fr_canonical(P->delta) ||
+        !fr_canonical(P->tau)) {
+      ctx->err = "sound setup: a parameter is not a canonical Fr (>= r)";
+      return ZK_ERR_ARG;
+    }
+    if (nshards != 1) return ZK_ERR_ARG;
+    t = host::fr_to_mont(P->tau.l);
+    alf = host::fr_to_mont(P->alpha.l);
+    bef = host::fr_to_mont(P->beta.l);
+    dinv = host::fr_inv(host::fr_to_mont(P->delta.l));
+    ginv = host::fr_inv(host::fr_to_mont(P->gamma.l));
+    const host::Fr zt = vanishing_at(t, log_n);
+    if (host::fr_is_zero(zt)) {
+      ctx->err = "sound setup: tau lies on the evaluation domain (Z(tau) = 0)";
+      return ZK_ERR_SETUP_PARAMS;
+    }
+    hk = host::fr_mul(zt, dinv);
+  } else {
+    t = host::fr_from_u64(ta);
+    alf = host::fr_from_u64(al);
+    bef = host::fr_from_u64(be);
+    dinv = host::fr_inv(host::fr_from_u64(de));
+    ginv = host::fr_inv(host::fr_from_u64(ga));
+    hk = dinv;
+  }
 
   // ---- Lagrange basis at tau~ and A_i, B_i, C_i (device) ----
   DevBuf wpow, L, abc[3];
@@ -386,29 +485,37 @@ int setup_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_setup_params* P, uint
     ZK_HIP(hipStreamSynchronize(st));  // host vectors / staging die here
   }
 
-  // ---- lo64 scalars ----
+  // ---- lo64 scalars (sound: whole canonical scalars, 4 words each) ----
   const uint64_t nic = V - num_public - 1, nvk = num_public + 1;
   DevBuf sa, sb, sic, svk, sh, tp;
-  sa.ensure(8 * V);
-  sb.ensure(8 * V);
-  sic.ensure(8 * std::max<uint64_t>(nic, 1));
-  svk.ensure(8 * nvk);
-  sh.ensure(8 * n);
+  sa.ensure(8 * sw * V);
+  sb.ensure(8 * sw * V);
+  sic.ensure(8 * sw * std::max<uint64_t>(nic, 1));
+  svk.ensure(8 * sw * nvk);
+  sh.ensure(8 * sw * n);
   tp.ensure(sizeof(Fr) * n);
   SetupConsts K;
-  K.al = fr_dev(host::fr_from_u64(al));
-  K.be = fr_dev(host::fr_from_u64(be));
+  K.al = fr_dev(alf);
+  K.be = fr_dev(bef);
   K.dinv = fr_dev(dinv);
   K.ginv = fr_dev(ginv);
   K.V = V;
   K.num_public = num_public;
-  k_setup_scalars<<<ceil_div(V, 256), 256, 0, st>>>(abc[0].as<Fr>(), abc[1].as<Fr>(), abc[2].as<Fr>(), K,
-                                                    sa.as<uint64_t>(), sb.as<uint64_t>(), sic.as<uint64_t>(),
-                                                    svk.as<uint64_t>());
+  if (sound)
+    k_setup_scalars_full<<<ceil_div(V, 256), 256, 0, st>>>(abc[0].as<Fr>(), abc[1].as<Fr>(), abc[2].as<Fr>(), K,
+                                                           sa.as<Fr>(), sb.as<Fr>(), sic.as<Fr>(), svk.as<Fr>());
+  else
+    k_setup_scalars<<<ceil_div(V, 256), 256, 0, st>>>(abc[0].as<Fr>(), abc[1].as<Fr>(), abc[2].as<Fr>(), K,
+                                                      sa.as<uint64_t>(), sb.as<uint64_t>(), sic.as<uint64_t>(),
+                                                      svk.as<uint64_t>());
   ZK_LAUNCH_CHECK();
-  fr_powers(tp.as<Fr>(), fr_dev(t), fr_dev(dinv), n, st);   // t~^i / d~
-  k_lo64<<<ceil_div(n, 256), 256, 0, st>>>(tp.as<Fr>(), n, sh.as<uint64_t>());
-  ZK_LAUNCH_CHECK();
+  fr_powers(tp.as<Fr>(), fr_dev(t), fr_dev(hk), n, st);   // t~^i / d~ (sound: tau^i Z(tau) / delta)
+  if (sound) {
+    fr_from_mont(tp.as<Fr>(), sh.as<uint64_t>(), n, st);
+  } else {
+    k_lo64<<<ceil_div(n, 256), 256, 0, st>>>(tp.as<Fr>(), n, sh.as<uint64_t>());
+    ZK_LAUNCH_CHECK();
+  }
 
   // ---- full-width generator multiples (host; setup:166-171) ----
   const auto G1h = g1_gen_host();
@@ -431,7 +538,7 @@ int setup_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_setup_params* P, uint
     vk->ic_len = nvk;
     DevBuf o;
     o.ensure(sizeof(G1A) * nvk);
-    fixed_base<G1>(ctx, svk.as<uint64_t>(), nullptr, nvk, o.as<G1A>(), st);
+    fixed_base<G1>(ctx, svk.as<uint64_t>(), nullptr, nvk, o.as<G1A>(), st, sw);
     to_abi<G1>(o.as<G1A>(), nvk, vk->ic_g1, st);
   }
 
@@ -450,44 +557,49 @@ int setup_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_setup_params* P, uint
     pk_host->h_len = n;
     DevBuf o;
     o.ensure(sizeof(G2A) * std::max<uint64_t>(V, n));
-    fixed_base<G1>(ctx, sa.as<uint64_t>(), nullptr, V, o.as<G1A>(), st);
+    fixed_base<G1>(ctx, sa.as<uint64_t>(), nullptr, V, o.as<G1A>(), st, sw);
     to_abi<G1>(o.as<G1A>(), V, pk_host->a_g1, st);
-    fixed_base<G1>(ctx, sb.as<uint64_t>(), nullptr, V, o.as<G1A>(), st);
+    fixed_base<G1>(ctx, sb.as<uint64_t>(), nullptr, V, o.as<G1A>(), st, sw);
     to_abi<G1>(o.as<G1A>(), V, pk_host->b_g1, st);
-    fixed_base<G2>(ctx, sb.as<uint64_t>(), nullptr, V, o.as<G2A>(), st);
+    fixed_base<G2>(ctx, sb.as<uint64_t>(), nullptr, V, o.as<G2A>(), st, sw);
     to_abi<G2>(o.as<G2A>(), V, pk_host->b_g2, st);
-    fixed_base<G1>(ctx, sic.as<uint64_t>(), nullptr, nic, o.as<G1A>(), st);
+    fixed_base<G1>(ctx, sic.as<uint64_t>(), nullptr, nic, o.as<G1A>(), st, sw);
     to_abi<G1>(o.as<G1A>(), nic, pk_host->ic_g1, st);
-    fixed_base<G1>(ctx, sh.as<uint64_t>(), nullptr, n, o.as<G1A>(), st);
+    fixed_base<G1>(ctx, sh.as<uint64_t>(), nullptr, n, o.as<G1A>(), st, sw);
     to_abi<G1>(o.as<G1A>(), n, pk_host->h_g1, st);
     return ZK_OK;
   }
 
   // ---- device-resident (optionally sharded) proving key ----
-  std::unique_ptr<zk_pk_dev> d = pk_create(ctx, q, num_public, shard, nshards);
+  std::unique_ptr<zk_pk_dev> d = pk_create(ctx, q, num_public, shard, nshards, sound);
   // host copies of the scalar vectors decide which bases are the identity
-  // (scalar 0 <=> identity, since every scalar is < 2^64 < r)
-  std::vector<uint64_t> ha(V), hb(V), hic(nic), hh(n);
-  ZK_HIP(hipMemcpyAsync(ha.data(), sa.p, 8 * V, hipMemcpyDeviceToHost, st));
-  ZK_HIP(hipMemcpyAsync(hb.data(), sb.p, 8 * V, hipMemcpyDeviceToHost, st));
-  if (nic) ZK_HIP(hipMemcpyAsync(hic.data(), sic.p, 8 * nic, hipMemcpyDeviceToHost, st));
-  ZK_HIP(hipMemcpyAsync(hh.data(), sh.p, 8 * n, hipMemcpyDeviceToHost, st));
+  // (scalar 0 <=> identity, since every scalar is < 2^64 < r; sound: a whole
+  // canonical scalar < r, sw words of it)
+  std::vector<uint64_t> ha(V * sw), hb(V * sw), hic(nic * sw), hh(n * sw);
+  ZK_HIP(hipMemcpyAsync(ha.data(), sa.p, 8 * sw * V, hipMemcpyDeviceToHost, st));
+  ZK_HIP(hipMemcpyAsync(hb.data(), sb.p, 8 * sw * V, hipMemcpyDeviceToHost, st));
+  if (nic) ZK_HIP(hipMemcpyAsync(hic.data(), sic.p, 8 * sw * nic, hipMemcpyDeviceToHost, st));
+  ZK_HIP(hipMemcpyAsync(hh.data(), sh.p, 8 * sw * n, hipMemcpyDeviceToHost, st));
   ZK_HIP(hipStreamSynchronize(st));
   const std::vector<uint8_t> own = var_owner(q, n, nshards);
-  const KeyExtras ex = key_extras(shard, alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2);
+  const KeyExtras ex = key_extras(shard, alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2, sound);
   // one base vector: G * (the device scalars at this shard's positions)
   auto build_slot = [&](const SlotShape& shape, const std::vector<uint64_t>& hs, const DevBuf& ds) {
-    std::vector<uint8_t> zero(hs.size());
-    for (size_t i = 0; i < hs.size(); i++) zero[i] = hs[i] == 0;
+    std::vector<uint8_t> zero(hs.size() / sw);
+    for (size_t i = 0; i < zero.size(); i++) {
+      uint64_t any = 0;
+      for (int k = 0; k < sw; k++) any |= hs[i * sw + k];
+      zero[i] = any == 0;
+    }
     const std::vector<uint32_t> pos = shard_positions(shape, shard, nshards, own, zero.data(), 1);
     pk_fill_slot(*d, shape, pos, ex, st, [&](const std::vector<uint32_t>& kept, void* d_out) {
       DevBuf dpos;
       dpos.ensure(sizeof(uint32_t) * kept.size());
       ZK_HIP(hipMemcpyAsync(dpos.p, kept.data(), sizeof(uint32_t) * kept.size(), hipMemcpyHostToDevice, st));
       if (shape.slot == MSM_B2)
-        fixed_base<G2>(ctx, ds.as<uint64_t>(), dpos.as<uint32_t>(), kept.size(), static_cast<G2A*>(d_out), st);
+        fixed_base<G2>(ctx, ds.as<uint64_t>(), dpos.as<uint32_t>(), kept.size(), static_cast<G2A*>(d_out), st, sw);
       else
-        fixed_base<G1>(ctx, ds.as<uint64_t>(), dpos.as<uint32_t>(), kept.size(), static_cast<G1A*>(d_out), st);
+        fixed_base<G1>(ctx, ds.as<uint64_t>(), dpos.as<uint32_t>(), kept.size(), static_cast<G1A*>(d_out), st, sw);
       ZK_HIP(hipStreamSynchronize(st));  // dpos dies here
     });
   };

@@ -89,6 +89,16 @@ int zk_test_pk_bases(zk_ctx* ctx, const zk_pk_dev* pk, int slot, int window, uin
   })
 }
 
+// ---- the 255-bit fixed-base kernel of a sound setup on its own ------------
+int zk_test_fixed_base_g1(zk_ctx* ctx, const zk_fr* scalars, size_t n, zk_g1_affine* out) {
+  if (!ctx || (n && (!scalars || !out))) return ZK_ERR_ARG;
+  ZK_TGUARD(ctx, { return fixed_base_wide_host(ctx, false, scalars, n, reinterpret_cast<uint64_t*>(out)); })
+}
+int zk_test_fixed_base_g2(zk_ctx* ctx, const zk_fr* scalars, size_t n, zk_g2_affine* out) {
+  if (!ctx || (n && (!scalars || !out))) return ZK_ERR_ARG;
+  ZK_TGUARD(ctx, { return fixed_base_wide_host(ctx, true, scalars, n, reinterpret_cast<uint64_t*>(out)); })
+}
+
 // ---- the square roots of points.hpp on their own ---------------------------
 namespace zk {
 // K = 1: Fq, K = 2: Fq2 (c0 then c1); canonical words in and out

@@ -35,6 +35,12 @@ A2 to_a(const X<Fq2>& p) {
   a.inf = !to_affine(p, a.x, a.y);
   return a;
 }
+// a 4-limb little-endian value is not a reduced Fr (>= r)
+bool geq_fr(const uint64_t* a) {
+  for (int i = 3; i >= 0; i--)
+    if (a[i] != FR_MOD64[i]) return a[i] > FR_MOD64[i];
+  return true;
+}
 A1 negate(const A1& p) {
   A1 r = p;
   if (!p.inf) r.y = neg(p.y);
@@ -44,14 +50,16 @@ A1 negate(const A1& p) {
 // [IC]_1 = ic_g1[0] + sum_i Fr::from(lo64(x_i)) ic_g1[i + 1] over the
 // non-zero lo64(x_i) (core:322-338; the MSM's result is the unique group
 // element, so a plain double-and-add gives the same point)
-int ic_sum(const zk_vk& vk, const zk_fr* in, size_t n, X<Fq>& out) {
+// whole: sound mode -- every x_i whole (canonical, checked by the caller)
+// instead of its lo64
+int ic_sum(const zk_vk& vk, const zk_fr* in, size_t n, X<Fq>& out, bool whole = false) {
   if (!vk.ic_g1 || vk.ic_len < n + 1) return ZK_ERR_ARG;   // the reference would index out of range
   A1 p;
   if (!load(vk.ic_g1[0], p)) return ZK_ERR_ARG;
   X<Fq> acc = to_x(p);
   for (size_t i = 0; i < n; i++) {
-    const uint64_t k[4] = {in[i].l[0], 0, 0, 0};
-    if (!k[0]) continue;
+    const uint64_t k[4] = {in[i].l[0], whole ? in[i].l[1] : 0, whole ? in[i].l[2] : 0, whole ? in[i].l[3] : 0};
+    if (!(k[0] | k[1] | k[2] | k[3])) continue;
     if (!load(vk.ic_g1[i + 1], p)) return ZK_ERR_ARG;
     acc = addp(acc, mul_scalar(to_x(p), k));
   }
@@ -211,20 +219,32 @@ int zk_pairing_product_is_one(const zk_g1_affine* g1, const zk_g2_affine* g2, si
   })
 }
 
-int zk_groth16_verify(const zk_vk* vk, const zk_proof* proof, const zk_fr* public_inputs, size_t n_inputs,
-                      int* valid) {
+static int verify_one(const zk_vk* vk, const zk_proof* proof, const zk_fr* public_inputs, size_t n_inputs,
+                      int* valid, bool sound) {
   if (!vk || !proof || !valid || (n_inputs && !public_inputs)) return ZK_ERR_ARG;
   ZK_HOST_GUARD({
     *valid = 0;
     if (n_inputs != vk->num_public) return ZK_ERR_INVALID_WITNESS;   // core:315-320
+    if (sound)   // a whole x_i must be a reduced Fr; the reference mode never looks past limb 0
+      for (size_t i = 0; i < n_inputs; i++)
+        if (geq_fr(public_inputs[i].l)) return ZK_ERR_ARG;
     X<Fq> ic;
-    const int rc = ic_sum(*vk, public_inputs, n_inputs, ic);
+    const int rc = ic_sum(*vk, public_inputs, n_inputs, ic, sound);
     if (rc) return rc;
     A1 a, c;
     A2 b;
     if (!load(proof->a, a) || !load(proof->b, b) || !load(proof->c, c)) return ZK_ERR_ARG;
     return pairing_check(*vk, a, b, to_a(ic), c, valid);
   })
+}
+
+int zk_groth16_verify(const zk_vk* vk, const zk_proof* proof, const zk_fr* public_inputs, size_t n_inputs,
+                      int* valid) {
+  return verify_one(vk, proof, public_inputs, n_inputs, valid, false);
+}
+int zk_groth16_verify_sound(const zk_vk* vk, const zk_proof* proof, const zk_fr* public_inputs, size_t n_inputs,
+                            int* valid) {
+  return verify_one(vk, proof, public_inputs, n_inputs, valid, true);
 }
 
 int zk_groth16_verify_batch(const zk_vk* vk, const zk_proof* proofs, const zk_fr* const* public_inputs,

@@ -149,6 +149,14 @@ int zk_ctx_set_schedule(zk_ctx *ctx, int schedule);
  *                         (zk_groth16_setup_sound_dev, zk_pk_upload_sound)
  *                         made after the call: ceil(255 / c) window copies
  *                         of every base; independent of ZK_OPT_PROVE_WIN_C
+ *   ZK_OPT_SOUND_COPIES   0 (default): a sound key made after the call keeps
+ *                         all W = ceil(255 / c) window copies of every base;
+ *                         k >= 1: it keeps min(k, W) of them and its MSMs sum
+ *                         window w over copy w mod k into bucket set w / k --
+ *                         k / W of the base memory against ceil(W / k) bucket
+ *                         reductions per MSM (zk_pk_device_bytes shows the
+ *                         key's size); negative: ZK_ERR_ARG.  Independent of
+ *                         ZK_OPT_SOUND_WIN_C; no effect on reference-mode keys
  *   ZK_OPT_EXCHANGE_TIMEOUT_MS  watchdog of the attached exchange (default
  *                         60000, >= 1): a distributed-quotient proof whose
  *                         peers do not answer within it fails with
@@ -179,7 +187,7 @@ int zk_ctx_set_schedule(zk_ctx *ctx, int schedule);
  * -- live in a separate library, include/zkp_test.h.) */
 enum { ZK_OPT_QUOTIENT_PATH = 1, ZK_OPT_PROVE_WIN_C = 2, ZK_OPT_EXCHANGE_TIMEOUT_MS = 3,
        ZK_OPT_DIST_QUOTIENT = 5, ZK_OPT_EXCHANGE_FIRST = 6, ZK_OPT_POINT_CHUNK = 7,
-       ZK_OPT_VERIFY_CHUNK = 8, ZK_OPT_SOUND_WIN_C = 9 };
+       ZK_OPT_VERIFY_CHUNK = 8, ZK_OPT_SOUND_WIN_C = 9, ZK_OPT_SOUND_COPIES = 10 };
 int zk_ctx_set_option(zk_ctx *ctx, int option, int64_t value);
 
 /* ---------------------------------------------------------------- MSM --- */
@@ -217,6 +225,16 @@ int zk_msm_g1_upload_windows(zk_ctx *ctx, const zk_g1_affine *bases, size_t n, u
                              zk_msm_bases **out);
 int zk_msm_g2_upload_windows(zk_ctx *ctx, const zk_g2_affine *bases, size_t n, uint32_t scalar_bits,
                              zk_msm_bases **out);
+/* Same, keeping only the first min(copies, W) of the W = ceil(scalar_bits / c)
+ * copies (copies = 0: all W, which is zk_msm_*_upload_windows).  Later
+ * zk_msm_*_dev calls sum digit window w over copy w mod copies into bucket
+ * set w / copies: ceil(W / copies) bucket sets and reductions instead of one,
+ * for copies x the base memory instead of W x.  The sum is the same element
+ * whatever the number of copies.  No reference counterpart. */
+int zk_msm_g1_upload_copies(zk_ctx *ctx, const zk_g1_affine *bases, size_t n, uint32_t scalar_bits,
+                            uint32_t copies, zk_msm_bases **out);
+int zk_msm_g2_upload_copies(zk_ctx *ctx, const zk_g2_affine *bases, size_t n, uint32_t scalar_bits,
+                            uint32_t copies, zk_msm_bases **out);
 void zk_msm_bases_free(zk_msm_bases *b);
 int zk_msm_g1_dev(zk_ctx *ctx, const zk_msm_bases *bases, const void *d_scalars, size_t n,
                   uint32_t scalar_bits, zk_g1_affine *out);
@@ -267,13 +285,16 @@ int zk_groth16_setup_dev(zk_ctx *ctx, const zk_r1cs_csr *qap, const zk_setup_par
  * ZK_ERR_SETUP_PARAMS.  No reference counterpart: the reference truncates. */
 int zk_groth16_setup_sound(zk_ctx *ctx, const zk_r1cs_csr *qap, const zk_setup_params *params,
                            uint64_t num_public, zk_pk *pk, zk_vk *vk);
-/* zk_groth16_setup_dev in sound mode: the device key holds ceil(255 / c)
- * window copies of every base (ZK_OPT_SOUND_WIN_C; c = 20: 13 copies, 128 B
- * per G1 and 256 B per G2 point -- about 14 GB at 2^20 constraints of the
- * synthetic circuit).  A key that does not fit the device comes back as
- * ZK_ERR_DEVICE with the failed allocation in zk_last_error; more than 2^31
- * window bases in one MSM as ZK_ERR_ARG.  Never sharded.  No reference
- * counterpart: the reference truncates. */
+/* zk_groth16_setup_dev in sound mode: the device key holds S window copies
+ * of every base, S = W = ceil(255 / c) by default (ZK_OPT_SOUND_WIN_C; c = 20:
+ * 13 copies, 128 B per G1 and 256 B per G2 point -- 1024 n S bytes for n
+ * constraints of the synthetic circuit, about 14 GB at 2^20) or fewer under
+ * ZK_OPT_SOUND_COPIES, which is how a key too large for the device with all
+ * its copies (2^24 constraints: 224 GB) is made to fit.  A key that still
+ * does not fit comes back as ZK_ERR_DEVICE with the failed allocation and
+ * that option named in zk_last_error; more than 2^31 copied bases in one MSM
+ * as ZK_ERR_ARG.  Never sharded.  No reference counterpart: the reference
+ * truncates. */
 int zk_groth16_setup_sound_dev(zk_ctx *ctx, const zk_r1cs_csr *qap, const zk_setup_params *params,
                                uint64_t num_public, zk_pk_dev **pk_out, zk_vk *vk);
 /* zk_pk_upload for a key made by zk_groth16_setup_sound.  zk_groth16_prove and
@@ -286,6 +307,11 @@ int zk_pk_upload_sound(zk_ctx *ctx, const zk_pk *pk, const zk_r1cs_csr *qap, zk_
 /* 1 for a sound device key, 0 for a reference-mode one (or NULL).  No
  * reference counterpart. */
 int zk_pk_is_sound(const zk_pk_dev *pk);
+/* Device memory a key of either mode holds, in bytes: its (window copies of
+ * the) bases, their variable indices and the constraint matrices.  What
+ * ZK_OPT_SOUND_COPIES trades is read here.  ZK_ERR_ARG for a NULL argument.
+ * No reference counterpart. */
+int zk_pk_device_bytes(const zk_pk_dev *pk, uint64_t *bytes);
 
 /* -------------------------------------------------------------- prove --- */
 /* Upload a proving key + its constraint system once; it stays resident.

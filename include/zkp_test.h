@@ -38,7 +38,8 @@ int zk_test_fault_after_exchange(zk_ctx *ctx, int k);
  * *nextras = extra bases appended after them (shard 0: alpha_1 and
  * 2^(64k) delta_1 / beta_2 and 2^(64k) delta_2 / beta_1; a sound key:
  * alpha_1, delta_1 / beta_2, delta_2 / beta_1, and ceil(255 / win_c)
- * windows).  With cap >=
+ * windows).  window < the copies the key holds (zk_test_pk_plan: every
+ * window unless the key was made under ZK_OPT_SOUND_COPIES).  With cap >=
  * count + nextras: idx_out[k] = the variable (H: coefficient) index of base
  * k < count, words_out = all count + nextras bases as canonical ABI words
  * (13 per G1, 25 per G2 point).  cap = 0 only queries the counts. */
@@ -46,6 +47,10 @@ int zk_test_pk_bases(zk_ctx *ctx, const zk_pk_dev *pk, int slot, int window, uin
                      uint64_t *words_out, size_t cap, size_t *count, size_t *nextras);
 /* The key's window plan and shard: win copies of c = win_c bits. */
 int zk_test_pk_info(const zk_pk_dev *pk, uint32_t *win, uint32_t *win_c, uint32_t *shard, uint32_t *nshards);
+/* The copies of every base the key holds (win unless ZK_OPT_SOUND_COPIES
+ * kept fewer) and the bucket sets of each of its prove MSMs,
+ * ceil(win / copies). */
+int zk_test_pk_plan(const zk_pk_dev *pk, uint32_t *copies, uint32_t *sets);
 /* The 255-bit fixed-base kernel of a sound setup (csrc/setup.hip,
  * k_fixed_base_wide) on its own, one lane per scalar: out[i] = scalars[i] G
  * for n whole canonical scalars, G the G1 generator.  A scalar >= r is

@@ -6,15 +6,25 @@ setup parameters, a device witness:
   setup   CRS.generate_device (straight into HBM, window copies included) at
           each --setup-log-n, reference mode and sound mode in turn: median of
           --setup-runs timed calls after one untimed one
-  prove   at --log-n: the reference-mode key, then a sound key per
-          ZK_OPT_SOUND_WIN_C in --win-c.  Each: --warmup untimed proofs, then
-          the median of --runs timed Prover.prove_device calls (overlapped
-          schedule, host wall time of the whole call, proof on the host), then
-          --serial-runs proofs under schedule 3 with zk_ctx_profile: device ms
-          per phase and per MSM (A, B1, B2, ICH; reference: AB, B2, ICH), per
-          proof.  Every sound proof is checked by Verifier.verify once.
+  prove   at --log-n: the reference-mode key (unless --no-reference), then a
+          sound key per ZK_OPT_SOUND_WIN_C in --win-c and per
+          ZK_OPT_SOUND_COPIES in --copies (0: every window copy, the shared
+          plan; k: the grouped-window plan over k copies).  Each: the GPU
+          setup timed like the setups above, the key's device_bytes(),
+          --warmup untimed proofs, then the median of --runs timed
+          Prover.prove_device calls (overlapped schedule, host wall time of
+          the whole call, proof on the host), then --serial-runs proofs under
+          schedule 3 with zk_ctx_profile: device ms per phase and per MSM (A,
+          B1, B2, ICH; reference: AB, B2, ICH), per proof.  Every sound proof
+          is checked by Verifier.verify once; a rejected proof fails the run.
 
   python tools/sound_bench.py [--out profiles/sound_prove_bench.json]
+  python tools/sound_bench.py --setup-log-n --win-c 16 20 --copies 1 2 4 0 --out sweep.json
+  python tools/sound_bench.py --setup-log-n --no-reference --log-n 24 --win-c 16 --copies 4 \\
+      --setup-runs 1 --out one_plan_2p24.json      # one timed setup, no untimed one before it
+
+A library given by ZK_AMD_LIB (an A/B build of another revision) may lack the
+copies option: it then runs --copies 0 only.
 """
 import argparse
 import importlib
@@ -62,11 +72,25 @@ def serial_profile(zkp, ctx, prove, runs):
             "gpu_span_ms": phases.get("prove_gpu_span")}
 
 
+def write(res, path):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+def plan_name(c, copies):
+    return "c%d" % c if not copies else "c%d_s%d" % (c, copies)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log-n", type=int, default=20)
-    ap.add_argument("--setup-log-n", type=int, nargs="+", default=[16, 20])
+    ap.add_argument("--setup-log-n", type=int, nargs="*", default=[16, 20])
     ap.add_argument("--win-c", type=int, nargs="+", default=[16, 20, 22])
+    ap.add_argument("--copies", type=int, nargs="+", default=[0],
+                    help="ZK_OPT_SOUND_COPIES per sound key: 0 every window copy, k the first k")
+    ap.add_argument("--no-reference", action="store_true", help="skip the reference-mode key")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--serial-runs", type=int, default=3)
@@ -78,7 +102,11 @@ def main():
 
     zkp = importlib.import_module("zero-knowledge-proofs_amd")
     import pyref
-    bid = zkp.check_build()
+    other = bool(os.environ.get("ZK_AMD_LIB"))
+    bid = zkp.build_id() if other else zkp.check_build()
+    has_copies = hasattr(zkp.lib(), "zk_pk_device_bytes")
+    if not has_copies and any(args.copies):
+        ap.error("this library has no ZK_OPT_SOUND_COPIES: --copies 0 only")
     rng = pyref.SplitMix64(0x50B3)
     params = zkp.SetupParams(*[rng.fr() for _ in range(5)])
     r, s = rng.fr(), rng.fr()
@@ -96,46 +124,73 @@ def main():
                 print("setup 2^%d %s" % (log_n, "sound" if sound else "reference"), json.dumps(t), flush=True)
 
         # ---- prove
-        n = 1 << args.log_n
-        qap = zkp.QAP(zkp.CSRMatrices.synthetic(n))
-        z = ctx.synthetic_witness(n, 0x50B4)
-        zlen = 3 * n + 1
+        def workload(log_n):
+            n = 1 << log_n
+            return zkp.QAP(zkp.CSRMatrices.synthetic(n)), ctx.synthetic_witness(n, 0x50B4), 3 * n + 1
 
-        def bench_key(dpk):
+        def bench_key(dpk, z, zlen):
             def prove():
                 return zkp.Prover.prove_device(dpk, z.data_ptr(), zlen, 1, r, s)
             out = median_ms(prove, args.warmup, args.runs)
             out["serial"] = serial_profile(zkp, ctx, prove, args.serial_runs)
-            out["win"], out["win_c"] = dpk.test_info()[:2]
+            if not other:
+                out["win"], out["win_c"] = dpk.test_info()[:2]
             return out, prove()
 
-        dpk = zkp.CRS.generate_device(ctx, qap, params, 1)
-        ref, _ = bench_key(dpk)
-        dpk.free()
-        res["prove_reference"] = ref
-        print("prove reference", json.dumps({k: v for k, v in ref.items() if k != "serial"}),
-              json.dumps(ref["serial"]["per_msm_ms"]), flush=True)
-
-        vk = zkp.VerificationKey(1, sound=True)
-        x = [zkp.from_limbs(z[1].cpu().numpy().view("uint64"))]
-        for c in args.win_c:
+        def bench_sound(qap, z, zlen, c, copies, setup_runs):
+            """One sound key: timed GPU setups, its size, prove times, one verified proof."""
             ctx.set_option(zkp.ZK_OPT_SOUND_WIN_C, c)
-            dpk = zkp.CRS.generate_device(ctx, qap, params, 1, sound=True, vk=vk)
-            out, proof = bench_key(dpk)
-            dpk.free()
-            assert zkp.Verifier.verify(vk, proof, x), "sound proof rejected"
-            out["over_reference"] = out["median_ms"] / ref["median_ms"]
-            res["prove_sound_c%d" % c] = out
-            print("prove sound c=%d" % c, json.dumps({k: v for k, v in out.items() if k != "serial"}),
-                  json.dumps(out["serial"]["per_msm_ms"]), flush=True)
-        ctx.set_option(zkp.ZK_OPT_SOUND_WIN_C, 0)
-        best = min(args.win_c, key=lambda c: res["prove_sound_c%d" % c]["median_ms"])
-        res["fastest_win_c"] = best
+            if has_copies:
+                ctx.set_option(zkp.ZK_OPT_SOUND_COPIES, copies)
+            vk = zkp.VerificationKey(1, sound=True)
+            made = []
 
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1, sort_keys=True)
-        f.write("\n")
+            def setup():
+                if made:
+                    made.pop().free()
+                made.append(zkp.CRS.generate_device(ctx, qap, params, 1, sound=True, vk=vk))
+            t_setup = median_ms(setup, 1 if setup_runs > 1 else 0, setup_runs)
+            dpk = made.pop()
+            out, proof = bench_key(dpk, z, zlen)
+            out["setup"] = t_setup
+            if has_copies:
+                out["copies"], out["sets"] = dpk.test_plan()
+                out["device_bytes"] = dpk.device_bytes()
+            dpk.free()
+            x = [zkp.from_limbs(z[1].cpu().numpy().view("uint64"))]
+            if not zkp.Verifier.verify(vk, proof, x):
+                raise SystemExit("sound proof rejected (c = %d, copies = %d)" % (c, copies))
+            out["verified"] = True
+            return out
+
+        def show(name, out):
+            print(name, json.dumps({k: v for k, v in out.items() if k != "serial"}),
+                  json.dumps(out["serial"]["per_msm_ms"]), flush=True)
+
+        qap, z, zlen = workload(args.log_n)
+        ref = None
+        if not args.no_reference:
+            dpk = zkp.CRS.generate_device(ctx, qap, params, 1)
+            ref, _ = bench_key(dpk, z, zlen)
+            dpk.free()
+            res["prove_reference"] = ref
+            show("prove reference", ref)
+
+        plans = [(c, k) for c in args.win_c for k in args.copies]
+        for c, k in plans:
+            out = bench_sound(qap, z, zlen, c, k, args.setup_runs)
+            if ref:
+                out["over_reference"] = out["median_ms"] / ref["median_ms"]
+            res["prove_sound_" + plan_name(c, k)] = out
+            show("prove sound c=%d copies=%d" % (c, k), out)
+        best = min(plans, key=lambda p: res["prove_sound_" + plan_name(*p)]["median_ms"])
+        res["fastest_win_c"] = best[0]
+        res["fastest_copies"] = best[1]
+        ctx.set_option(zkp.ZK_OPT_SOUND_WIN_C, 0)
+        if has_copies:
+            ctx.set_option(zkp.ZK_OPT_SOUND_COPIES, 0)
+
+    write(res, args.out)
     print(json.dumps({k: v for k, v in res.items() if not k.startswith("prove_")}))
 
 

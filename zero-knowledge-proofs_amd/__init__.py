@@ -58,16 +58,18 @@ EXPORTS = (
     "zk_groth16_verify_many", "zk_pairing_products",
     "zk_groth16_setup_sound", "zk_groth16_setup_sound_dev", "zk_pk_upload_sound", "zk_pk_is_sound",
     "zk_groth16_verify_sound", "zk_groth16_verify_many_sound",
+    "zk_msm_g1_upload_copies", "zk_msm_g2_upload_copies", "zk_pk_device_bytes",
 )
 # include/zkp_test.h (libzkp_amd_test.so)
 TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fault_after_exchange",
-                "zk_test_pk_bases", "zk_test_pk_info", "zk_test_fq_sqrt", "zk_test_fq2_sqrt",
+                "zk_test_pk_bases", "zk_test_pk_info", "zk_test_pk_plan", "zk_test_fq_sqrt", "zk_test_fq2_sqrt",
                 "zk_test_fq12", "zk_test_pairing_gt", "zk_test_fixed_base_g1", "zk_test_fixed_base_g2")
 ZK_OPT_QUOTIENT_PATH, ZK_OPT_PROVE_WIN_C, ZK_OPT_EXCHANGE_TIMEOUT_MS, ZK_OPT_DIST_QUOTIENT = 1, 2, 3, 5
 ZK_OPT_EXCHANGE_FIRST = 6
 ZK_OPT_POINT_CHUNK = 7
 ZK_OPT_VERIFY_CHUNK = 8
 ZK_OPT_SOUND_WIN_C = 9
+ZK_OPT_SOUND_COPIES = 10
 # zk_verify_status: what a proof / pairing product of a GPU batch call can be
 ZK_VERIFY_REJECT, ZK_VERIFY_ACCEPT, ZK_VERIFY_MALFORMED = range(3)
 # ops of zk_test_fq12 (include/zkp_test.h); FINAL_EXP computes a^(FINAL_EXP_C (p^12 - 1) / r)
@@ -406,7 +408,9 @@ class Context:
         """zk_ctx_set_option: ZK_OPT_QUOTIENT_PATH (-1 by size, 0 small-domain,
         1 large-domain), ZK_OPT_PROVE_WIN_C (0 by size, 16, 22; keys made
         afterwards), ZK_OPT_SOUND_WIN_C (0 the default, 16, 20, 22; sound
-        keys made afterwards), ZK_OPT_EXCHANGE_TIMEOUT_MS (>= 1), ZK_OPT_DIST_QUOTIENT
+        keys made afterwards), ZK_OPT_SOUND_COPIES (0 every window copy, k >= 1
+        at most k copies of every base; sound keys made afterwards),
+        ZK_OPT_EXCHANGE_TIMEOUT_MS (>= 1), ZK_OPT_DIST_QUOTIENT
         (-1 distributed when an exchange of the key's shape is attached, 0
         replicated), ZK_OPT_EXCHANGE_FIRST (0 MSMs start with the witness, 1
         they wait for the distributed quotient), ZK_OPT_POINT_CHUNK (points
@@ -472,6 +476,26 @@ class Context:
                              C.c_size_t(len(scalars)), C.c_uint32(scalar_bits), _p(out))
         _check(rc, self, "zk_msm_g2")
         return out
+
+    def msm_upload(self, bases, g2=False, scalar_bits=255, copies=None):
+        """Bases kept in HBM for repeated MSMs -> MsmBases.  copies=None: the
+        bases alone (zk_msm_*_upload); otherwise zk_msm_*_upload_copies with
+        window-shifted copies for scalars of at most scalar_bits bits: 0 all
+        W = ceil(scalar_bits / c) of them (one bucket set), k >= 1 min(k, W)
+        (ceil(W / k) bucket sets).  bases: (n, 13 | 25) uint64 canonical affine."""
+        words = G2_WORDS if g2 else G1_WORDS
+        bases = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, words)
+        h = C.c_void_p()
+        grp = "g2" if g2 else "g1"
+        if copies is None:
+            rc = getattr(lib(), f"zk_msm_{grp}_upload")(C.c_void_p(self._h), _p(bases), C.c_size_t(len(bases)),
+                                                        C.byref(h))
+        else:
+            rc = getattr(lib(), f"zk_msm_{grp}_upload_copies")(
+                C.c_void_p(self._h), _p(bases), C.c_size_t(len(bases)), C.c_uint32(int(scalar_bits)),
+                C.c_uint32(int(copies)), C.byref(h))
+        _check(rc, self, f"zk_msm_{grp}_upload")
+        return MsmBases(self, h.value, len(bases), g2)
 
     # ---- points of a key file (ark CanonicalDeserialize, Validate::Yes) ----
     def _decompress(self, name, data, enc, words):
@@ -988,6 +1012,37 @@ class VerificationKey:
             raise SetupError(str(e)) from None
 
 
+class MsmBases:
+    """MSM bases resident in HBM (zk_msm_bases), from Context.msm_upload."""
+
+    def __init__(self, ctx, handle, n, g2):
+        self.ctx, self._h, self.n, self.g2 = ctx, handle, n, g2
+
+    def msm(self, scalars, scalar_bits=255):
+        """zk_msm_g1_dev / zk_msm_g2_dev: sum_i scalars[i] * bases[i] -> 13 | 25
+        words.  scalars: (n, 4) canonical Fr, a numpy array (uploaded) or a
+        torch int64 tensor on the context's device."""
+        import torch
+        if isinstance(scalars, torch.Tensor):
+            d = scalars.contiguous()
+        else:
+            sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+            d = torch.from_numpy(sc.view(np.int64).copy()).to(f"cuda:{self.ctx.device}")
+        out = np.zeros(G2_WORDS if self.g2 else G1_WORDS, dtype=np.uint64)
+        fn = lib().zk_msm_g2_dev if self.g2 else lib().zk_msm_g1_dev
+        _check(fn(C.c_void_p(self.ctx._h), C.c_void_p(self._h), C.c_void_p(d.data_ptr()), C.c_size_t(len(d)),
+                  C.c_uint32(int(scalar_bits)), _p(out)), self.ctx, "zk_msm_dev")
+        return out
+
+    def free(self):
+        if getattr(self, "_h", None):
+            lib().zk_msm_bases_free(C.c_void_p(self._h))
+            self._h = None
+
+    def __del__(self):
+        self.free()
+
+
 class DeviceProvingKey:
     """A proving key resident in HBM (zk_pk_dev)."""
 
@@ -1031,6 +1086,19 @@ class DeviceProvingKey:
         v = [C.c_uint32() for _ in range(4)]
         _check(test_lib().zk_test_pk_info(C.c_void_p(self._h), *[C.byref(x) for x in v]), None, "zk_test_pk_info")
         return tuple(x.value for x in v)
+
+    def test_plan(self):
+        """zk_test_pk_plan (test library): (copies of every base the key
+        holds, bucket sets per prove MSM)."""
+        v = [C.c_uint32() for _ in range(2)]
+        _check(test_lib().zk_test_pk_plan(C.c_void_p(self._h), *[C.byref(x) for x in v]), None, "zk_test_pk_plan")
+        return tuple(x.value for x in v)
+
+    def device_bytes(self):
+        """zk_pk_device_bytes: device memory the key holds (bases, indices, CSR)."""
+        b = C.c_uint64()
+        _check(lib().zk_pk_device_bytes(C.c_void_p(self._h), C.byref(b)), None, "zk_pk_device_bytes")
+        return b.value
 
     def test_bases(self, slot, window=0):
         """zk_test_pk_bases (test library): (variable / coefficient index per

@@ -221,7 +221,9 @@ int zk_msm_g2(zk_ctx* ctx, const zk_g2_affine* bases, size_t nb, const zk_fr* sc
 // Window-shifted uploads (zk_msm_*_upload_windows): c = 16-bit digit windows,
 // W = ceil(scalar_bits / c) copies 2^(c w) P of every base, so every
 // later MSM of <= scalar_bits-bit scalars sums all its windows into ONE
-// bucket set (msm_launch_shared; the prove path's trick, prove.hip).
+// bucket set (msm_launch_grouped; the prove path's trick, prove.hip).
+// zk_msm_*_upload_copies keeps the first S < W copies only: S windows per
+// bucket set, ceil(W / S) sets.
 // Window width c: 16 up to 64-bit scalars (4 windows, 2^15 buckets), 20 for
 // wider ones -- 13 windows over 2^19 buckets instead of 16 over 2^15: the
 // 2^20 full-width MSM 3.79-3.87 vs 3.92-4.01 ms; c = 18, 19, 22 lose
@@ -233,7 +235,8 @@ int zk_msm_g2(zk_ctx* ctx, const zk_g2_affine* bases, size_t nb, const zk_fr* sc
 static int upload_win_c(uint32_t win_bits) { return win_bits > 64 ? ZK_UPLOAD_WIN_C : 16; }
 
 template <class C, class ABI>
-static int msm_upload(zk_ctx* ctx, const ABI* bases, size_t n, int group, uint32_t win_bits, zk_msm_bases** out) {
+static int msm_upload(zk_ctx* ctx, const ABI* bases, size_t n, int group, uint32_t win_bits, uint32_t copies,
+                      zk_msm_bases** out) {
   if (!ctx || !out) return ZK_ERR_ARG;
   if (win_bits > 256) return ZK_ERR_ARG;
   ZK_GUARD(ctx, {
@@ -243,18 +246,22 @@ static int msm_upload(zk_ctx* ctx, const ABI* bases, size_t n, int group, uint32
     b->n = n;
     const int MSM_UPLOAD_WIN_C = upload_win_c(win_bits);
     const int W = win_bits ? (int)((win_bits + MSM_UPLOAD_WIN_C - 1) / MSM_UPLOAD_WIN_C) : 1;
-    if ((uint64_t)n * W >= 0x7fffffffull) throw Error(ZK_ERR_ARG, "msm: too many window bases");
-    b->bases.ensure(sizeof(typename C::A) * std::max<size_t>(n * W, 1));
+    // the copies kept (0: all W): fewer than W and the MSMs run the grouped-window plan
+    const int S = copies ? (int)std::min<uint32_t>(copies, (uint32_t)W) : W;
+    // an MSM entry indexes a base of one of the copies in 31 bits
+    if ((uint64_t)n * S >= 0x7fffffffull) throw Error(ZK_ERR_ARG, "msm: too many window bases");
+    b->bases.ensure(sizeof(typename C::A) * std::max<size_t>(n * S, 1));
     DevBuf raw;
     raw.ensure(sizeof(ABI) * std::max<size_t>(n, 1));
     if (n) {
       ZK_HIP(hipMemcpyAsync(raw.p, bases, sizeof(ABI) * n, hipMemcpyHostToDevice, ctx->stream));
       convert_bases<C>(raw.as<uint64_t>(), b->bases.as<typename C::A>(), n, ctx->stream);
-      if (W > 1) msm_precompute_windows<C>(b->bases.as<typename C::A>(), n, W, MSM_UPLOAD_WIN_C, ctx->stream);
-      b->stride = msm_pad_bases<C>(b->bases, n * W, ctx->stream);
+      if (S > 1) msm_precompute_windows<C>(b->bases.as<typename C::A>(), n, S, MSM_UPLOAD_WIN_C, ctx->stream);
+      b->stride = msm_pad_bases<C>(b->bases, n * S, ctx->stream);
     }
     if (W > 1) {
       b->win = W;
+      b->copies = S;
       b->win_c = MSM_UPLOAD_WIN_C;
       b->win_bits = win_bits;
     }
@@ -264,18 +271,26 @@ static int msm_upload(zk_ctx* ctx, const ABI* bases, size_t n, int group, uint32
   })
 }
 int zk_msm_g1_upload(zk_ctx* ctx, const zk_g1_affine* bases, size_t n, zk_msm_bases** out) {
-  return msm_upload<G1>(ctx, bases, n, 1, 0, out);
+  return msm_upload<G1>(ctx, bases, n, 1, 0, 0, out);
 }
 int zk_msm_g2_upload(zk_ctx* ctx, const zk_g2_affine* bases, size_t n, zk_msm_bases** out) {
-  return msm_upload<G2>(ctx, bases, n, 2, 0, out);
+  return msm_upload<G2>(ctx, bases, n, 2, 0, 0, out);
 }
 int zk_msm_g1_upload_windows(zk_ctx* ctx, const zk_g1_affine* bases, size_t n, uint32_t scalar_bits,
                              zk_msm_bases** out) {
-  return msm_upload<G1>(ctx, bases, n, 1, scalar_bits ? scalar_bits : 255, out);
+  return zk_msm_g1_upload_copies(ctx, bases, n, scalar_bits, 0, out);
 }
 int zk_msm_g2_upload_windows(zk_ctx* ctx, const zk_g2_affine* bases, size_t n, uint32_t scalar_bits,
                              zk_msm_bases** out) {
-  return msm_upload<G2>(ctx, bases, n, 2, scalar_bits ? scalar_bits : 255, out);
+  return zk_msm_g2_upload_copies(ctx, bases, n, scalar_bits, 0, out);
+}
+int zk_msm_g1_upload_copies(zk_ctx* ctx, const zk_g1_affine* bases, size_t n, uint32_t scalar_bits, uint32_t copies,
+                            zk_msm_bases** out) {
+  return msm_upload<G1>(ctx, bases, n, 1, scalar_bits ? scalar_bits : 255, copies, out);
+}
+int zk_msm_g2_upload_copies(zk_ctx* ctx, const zk_g2_affine* bases, size_t n, uint32_t scalar_bits, uint32_t copies,
+                            zk_msm_bases** out) {
+  return msm_upload<G2>(ctx, bases, n, 2, scalar_bits ? scalar_bits : 255, copies, out);
 }
 void zk_msm_bases_free(zk_msm_bases* b) {
   if (!b) return;
@@ -320,8 +335,9 @@ static int msm_dev(zk_ctx* ctx, const zk_msm_bases* b, const void* d_sc, size_t 
     }
     MsmWork& w = ctx->msm[0];
     const int mbits = sw == 1 ? 64 : 255;
-    if (b->win > 1 && (uint32_t)mbits <= b->win_bits)   // one bucket set over the shifted copies
-      msm_launch_shared<C>(w, b->bases.as<typename C::A>(), sc, sw, (uint32_t)n, mbits, b->win_c, st, b->stride);
+    if (b->win > 1 && (uint32_t)mbits <= b->win_bits)   // one bucket set over the shifted copies, or one per b->copies windows
+      msm_launch_grouped<C>(w, b->bases.as<typename C::A>(), sc, sw, (uint32_t)n, mbits, b->win_c, b->copies, st,
+                            b->stride);
     else
       msm_launch<C>(w, b->bases.as<typename C::A>(), sc, sw, (uint32_t)n, mbits, st, b->stride);
     msm_download<C>(w, st);
@@ -467,6 +483,15 @@ int zk_pk_upload_sound(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs_csr* qap, zk_
   })
 }
 int zk_pk_is_sound(const zk_pk_dev* pk) { return pk && pk->sound() ? 1 : 0; }
+
+int zk_pk_device_bytes(const zk_pk_dev* pk, uint64_t* bytes) {
+  if (!pk || !bytes) return ZK_ERR_ARG;
+  uint64_t b = 0;
+  for (int k = 0; k < NUM_MSM; k++) b += pk->bases[k].bytes + pk->idx[k].bytes;
+  for (int m = 0; m < 3; m++) b += pk->csr.rp[m].bytes + pk->csr.col[m].bytes + pk->csr.val[m].bytes;
+  *bytes = b;
+  return ZK_OK;
+}
 
 int zk_pk_upload(zk_ctx* ctx, const zk_pk* pk, const zk_r1cs_csr* qap, zk_pk_dev** out) {
   if (!ctx || !pk || !qap || !out) return ZK_ERR_ARG;

@@ -62,6 +62,7 @@ struct zk_ctx {
   int quot_path = -1;                          // -1 by domain size, 0 small-domain, 1 large-domain
   int prove_win_c = 0;                         // 0 by size, else 16 or 22 (keys made after the call)
   int sound_win_c = 0;                         // sound keys: 0 the default, else 16, 20 or 22 (likewise)
+  int sound_copies = 0;                        // sound keys: 0 every window copy, else at most this many (likewise)
   double exch_timeout_ms = 60000;              // watchdog of an attached exchange
   int dist_quotient = -1;                      // -1 distributed when an exchange of the key's shape
                                                // is attached, 0 never (each rank the whole quotient)
@@ -91,13 +92,15 @@ struct zk_pk_dev {
   uint32_t count[zk::NUM_MSM] = {};  // compacted bases (without extras)
   uint32_t extras[zk::NUM_MSM] = {}; // extra bases appended (shard 0 only)
   // Window-shifted base copies (msm_precompute_windows): bases[slot] holds
-  // win x (count + extras) points, window w = 2^(win_c w) x the base,
-  // win = ceil(scalar_bits / win_c).
+  // copies x (count + extras) points, copy w = 2^(win_c w) x the base,
+  // win = ceil(scalar_bits / win_c) digit windows.  copies = win unless a
+  // sound key was made under ZK_OPT_SOUND_COPIES: its MSMs then run the
+  // grouped-window plan (msm_make_plan_grouped) over the copies it kept.
   // The IC and H vectors are ONE MSM of the prove (both terms of pi_C):
-  // bases[MSM_H] holds win x (count[IC] + count[H]) points, each window the
-  // IC bases then the H bases (ich_tot() per window), and bases[MSM_IC] is
-  // empty once the windows are built.
-  int win = 1, win_c = 0;
+  // bases[MSM_H] holds copies x (count[IC] + count[H]) points, each copy the
+  // IC bases then the H bases (ich_tot() per copy), and bases[MSM_IC] is
+  // empty once the copies are built.
+  int win = 1, win_c = 0, copies = 1;
   uint32_t ich_tot() const { return count[zk::MSM_IC] + extras[zk::MSM_IC] + count[zk::MSM_H] + extras[zk::MSM_H]; }
   // idx[MSM_H][k] == k for every compacted H base (an unsharded key without
   // identity H bases): the local quotient then writes lo64(H_i) straight
@@ -121,8 +124,8 @@ struct zk_msm_bases {
   int device = 0;
   int group = 1;  // 1 = G1, 2 = G2
   size_t n = 0;
-  zk::DevBuf bases;   // n points, or win x n window-shifted copies (window-major)
-  int win = 1, win_c = 0;
+  zk::DevBuf bases;   // n points, or copies x n window-shifted copies (copy-major)
+  int win = 1, win_c = 0, copies = 1;   // copies < win: the grouped-window plan
   uint32_t win_bits = 0;   // scalars up to this width use the shared bucket set
   uint32_t stride = 0;     // bytes between bases (0 = packed), see msm_pad_bases
 };

@@ -3,8 +3,9 @@
 // kernel + rocPRIM's onesweep radix sort + its passes).
 //
 // An entry is one (point, digit window) pair: its key is the bucket (shared
-// plans: segment base + |digit| - 1, a zero digit the segment's bucket 0
-// with the dummy entry; per-window plans: window base + |digit| - 1, a zero
+// plans: segment base, or the base of the window's bucket set in a grouped
+// plan, + |digit| - 1, a zero digit that bucket 0 with the dummy entry;
+// per-window plans: window base + |digit| - 1, a zero
 // digit key G, which sorts after every bucket), its value the base index
 // with the digit's sign in bit 31.  The accumulate needs the entries grouped
 // by key and off[] (the first entry of every bucket).  The key bits split
@@ -66,7 +67,24 @@ struct GsArgs {
   uint32_t tile0[MSM_MAXSEG + 1];   // first pass-0 tile of segment k
   uint32_t boff[MSM_MAXWIN];
   uint32_t nseg, nwin, c, bits, shared, G, M, rb;
+  uint32_t copies, setstride;   // shared plans: base copies S, keys from one bucket set to the next
 };
+
+// Where the entries of one window of a segment point in a shared plan
+// (MsmPlan::copies): ebase = the first base of copy w mod S (the entry of
+// point i is ebase + i), kbase = the first key of bucket set w / S.  Carried
+// from window to window beside the digit carry (gs_load), so that no entry
+// pays a division.  A per-window plan (a.shared == 0) carries it too and
+// never reads it (gs_entry takes boff[w] there): a branch per entry to skip
+// three integer operations would cost more than they do.
+struct GsWin {
+  uint32_t copy, ebase, kbase;
+};
+// The window after gw's; ioff, wstride: the segment's.
+ZK_DI GsWin gs_next_win(const GsArgs& a, GsWin gw, uint32_t ioff, uint32_t wstride) {
+  const bool wrap = gw.copy + 1 == a.copies;   // on to the next bucket set, back to copy 0
+  return {wrap ? 0u : gw.copy + 1, wrap ? ioff : gw.ebase + wstride, wrap ? gw.kbase + a.setstride : gw.kbase};
+}
 
 // Digit of window w of a scalar, given the carry out of window w - 1 (signed
 // windows, the top one unsigned), one window at a time.
@@ -85,12 +103,13 @@ ZK_DI uint32_t gs_digit(const GsArgs& a, uint32_t w, const uint64_t (&s)[SW], ui
   return v;
 }
 
-// The entry of (segment k, point i, window w) with digit magnitude mag.
-ZK_DI void gs_entry(const GsArgs& a, uint32_t k, uint32_t i, uint32_t w, uint32_t mag, bool neg, uint32_t& key,
+// The entry of (point i, window w) with digit magnitude mag; gw: where
+// window w of the point's segment points (shared plans).
+ZK_DI void gs_entry(const GsArgs& a, GsWin gw, uint32_t i, uint32_t w, uint32_t mag, bool neg, uint32_t& key,
                     uint32_t& ent) {
   if (a.shared) {
-    key = a.kbase[k] + (mag ? mag - 1 : 0u);
-    ent = mag ? ((w * a.wstride[k] + a.ioff[k] + i) | (neg ? 0x80000000u : 0u)) : MSM_DUMMY;
+    key = gw.kbase + (mag ? mag - 1 : 0u);
+    ent = mag ? ((gw.ebase + i) | (neg ? 0x80000000u : 0u)) : MSM_DUMMY;
   } else {
     key = mag ? a.boff[w] + mag - 1 : a.G;
     ent = i | (neg ? 0x80000000u : 0u);
@@ -129,18 +148,26 @@ ZK_DI void gs_load(const GsArgs& a, uint32_t tile, const uint32_t* __restrict__ 
     bool neg = false;
 #pragma unroll
     for (int j = 0; j < SW; j++) s[j] = i < nk ? a.sc[k][(size_t)i * SW + j] : 0ull;
-    for (uint32_t q = 0; q < w; q++) (void)gs_digit<SW>(a, q, s, carry, neg);
+    const uint32_t ioff = a.ioff[k], wstride = a.wstride[k];
+    const GsWin gw0{0u, ioff, a.kbase[k]};   // window 0: copy 0, bucket set 0
+    GsWin gw = gw0;
+    for (uint32_t q = 0; q < w; q++) {
+      (void)gs_digit<SW>(a, q, s, carry, neg);
+      gw = gs_next_win(a, gw, ioff, wstride);
+    }
 #pragma unroll
     for (uint32_t r = 0; r < GS_IPT; r++) {
       key[r] = ent[r] = 0;
       if (i < nk) {
         const uint32_t mag = gs_digit<SW>(a, w, s, carry, neg);
-        gs_entry(a, k, i, w, mag, neg, key[r], ent[r]);
+        gs_entry(a, gw, i, w, mag, neg, key[r], ent[r]);
         valid |= 1u << r;
       }
+      gw = gs_next_win(a, gw, ioff, wstride);
       if (++w == a.nwin) {   // next point round
         w = 0;
         carry = 0;
+        gw = gw0;
         i += 64;
 #pragma unroll
         for (int j = 0; j < SW; j++) s[j] = (r + 1 < GS_IPT && i < nk) ? a.sc[k][(size_t)i * SW + j] : 0ull;
@@ -359,14 +386,36 @@ __global__ void __launch_bounds__(GS_THREADS) k_gs_scatter(GsArgs a, uint32_t sh
 // off[g] = first sorted position with key >= g, for g in [0, G].
 // ctl (MsmWork::nbig): the merge's control words, zeroed here so that no
 // memset launch is needed.
+// Thread i <= M owns the buckets in (key[i-1], key[i]] (thread M: those after
+// the last key), all but the last of them empty.  A short run it writes
+// itself; a long one -- the unused part of a grouped plan's last bucket set
+// (the top window alone in it fills 2^top of its 2^(c-1) buckets: 491 k empty
+// ones at c = 20), or the buckets that skewed scalars leave empty -- is
+// written by the whole workgroup, 256 buckets a step, instead of one store
+// after another on one lane (7 ms per MSM for that tail at c = 20).
+constexpr uint32_t OFF_LONG_RUN = 64;
 __global__ void __launch_bounds__(256) k_msm_offsets(const uint32_t* __restrict__ key, uint32_t M, uint32_t G,
                                                      uint32_t* __restrict__ off, uint32_t* __restrict__ ctl) {
+  __shared__ uint32_t run_lo[256], run_hi[256], run_i[256], nrun;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < 2) ctl[i] = 0;
-  if (i > M) return;
-  const uint32_t lo = i ? min(key[i - 1], G) + 1 : 0;     // keys in (key[i-1], key[i]] start at i
-  const uint32_t hi = i < M ? min(key[i], G) : G;
-  for (uint32_t g = lo; g <= hi; g++) off[g] = i;
+  if (threadIdx.x == 0) nrun = 0;
+  __syncthreads();
+  if (i <= M) {
+    const uint32_t lo = i ? min(key[i - 1], G) + 1 : 0;     // keys in (key[i-1], key[i]] start at i
+    const uint32_t hi = i < M ? min(key[i], G) : G;
+    if (lo <= hi && hi - lo >= OFF_LONG_RUN) {
+      const uint32_t r = atomicAdd(&nrun, 1u);   // the runs are disjoint: their order does not matter
+      run_lo[r] = lo;
+      run_hi[r] = hi;
+      run_i[r] = i;
+    } else {
+      for (uint32_t g = lo; g <= hi; g++) off[g] = i;
+    }
+  }
+  __syncthreads();
+  for (uint32_t r = 0; r < nrun; r++)
+    for (uint32_t g = run_lo[r] + threadIdx.x; g <= run_hi[r]; g += 256) off[g] = run_i[r];
 }
 
 void msm_offsets(MsmWork& w, uint32_t M, hipStream_t st) {
@@ -432,6 +481,8 @@ void msm_group(MsmWork& w, const MsmSeg* segs, int nseg, int sw, hipStream_t st)
   a.bits = (uint32_t)p.bits;
   a.shared = p.shared ? 1u : 0u;
   a.G = p.G;
+  a.copies = p.shared ? (uint32_t)p.copies : 1u;
+  a.setstride = p.nb[0];
   for (int k = 0; k < p.nwin && k < MSM_MAXWIN; k++) a.boff[k] = p.boff[k];
   uint32_t tiles = 0;
   size_t M = 0;

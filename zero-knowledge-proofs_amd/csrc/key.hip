@@ -331,40 +331,60 @@ static int prove_win_c(const zk_ctx* ctx, const zk_pk_dev& pk) {
 constexpr int SOUND_WIN_C_DEFAULT = 20;
 static int sound_win_c(const zk_ctx* ctx) { return ctx->sound_win_c ? ctx->sound_win_c : SOUND_WIN_C_DEFAULT; }
 
+// The `copies` window copies of one MSM slot's bases (MSM_H: of [IC | H]),
+// padded to whole lines, in place of the bases themselves.
+static void pk_precompute_slot(zk_ctx* ctx, zk_pk_dev& pk, int slot, int win_c, int copies) {
+  hipStream_t st = ctx->stream;
+  const size_t n = slot == MSM_H ? pk.ich_tot() : (size_t)pk.count[slot] + pk.extras[slot];
+  const size_t asz = slot == MSM_B2 ? sizeof(G2A) : sizeof(G1A);
+  // every entry of an MSM indexes a base of one of the copies in 31 bits (msm.hip)
+  if ((uint64_t)n * copies >= MSM_DUMMY)
+    throw Error(ZK_ERR_ARG, "proving key: " + std::to_string(n) + " bases x " + std::to_string(copies) +
+                                " window copies exceed the 2^31 window bases of one MSM");
+  DevBuf big;
+  big.ensure(asz * std::max<size_t>(n * copies, 1));
+  if (slot == MSM_H) {   // [IC | H]
+    const size_t nic = (size_t)pk.count[MSM_IC] + pk.extras[MSM_IC], nh = n - nic;
+    if (nic) ZK_HIP(hipMemcpyAsync(big.p, pk.bases[MSM_IC].p, asz * nic, hipMemcpyDeviceToDevice, st));
+    if (nh)
+      ZK_HIP(hipMemcpyAsync(static_cast<char*>(big.p) + asz * nic, pk.bases[MSM_H].p, asz * nh,
+                            hipMemcpyDeviceToDevice, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    pk.bases[MSM_IC].release();
+  } else if (n) {
+    ZK_HIP(hipMemcpyAsync(big.p, pk.bases[slot].p, asz * n, hipMemcpyDeviceToDevice, st));
+  }
+  if (slot == MSM_B2) msm_precompute_windows<G2>(big.as<G2A>(), n, copies, win_c, st);
+  else msm_precompute_windows<G1>(big.as<G1A>(), n, copies, win_c, st);
+  ZK_HIP(hipStreamSynchronize(st));
+  pk.stride[slot] = slot == MSM_B2 ? msm_pad_bases<G2>(big, n * copies, st) : msm_pad_bases<G1>(big, n * copies, st);
+  pk.bases[slot] = std::move(big);
+}
+
+// zk_ctx_set_option(ZK_OPT_SOUND_COPIES) keeps only the first S of a sound
+// key's W copies: its MSMs then sum window w over copy w mod S into bucket
+// set w / S (msm_make_plan_grouped) -- S / W of the base memory against
+// ceil(W / S) bucket reductions per MSM.  A reference-mode
+// key keeps every copy: its batched MSMs own one bucket set each.
 static void pk_precompute_windows(zk_ctx* ctx, zk_pk_dev& pk) {
   const int PROVE_WIN_C = pk.sound() ? sound_win_c(ctx) : prove_win_c(ctx, pk);
   const int PROVE_WIN = ((int)pk.scalar_bits + PROVE_WIN_C - 1) / PROVE_WIN_C;
-  hipStream_t st = ctx->stream;
+  const int COPIES = pk.sound() && ctx->sound_copies ? std::min(ctx->sound_copies, PROVE_WIN) : PROVE_WIN;
   for (int slot = 0; slot < NUM_MSM; slot++) {
     if (slot == MSM_IC) continue;   // windowed together with H (zk_pk_dev::ich_tot)
-    const size_t n = slot == MSM_H ? pk.ich_tot() : (size_t)pk.count[slot] + pk.extras[slot];
-    const size_t asz = slot == MSM_B2 ? sizeof(G2A) : sizeof(G1A);
-    // every (point, window) entry of an MSM is a 31-bit index (msm.hip)
-    if ((uint64_t)n * PROVE_WIN >= MSM_DUMMY)
-      throw Error(ZK_ERR_ARG, "proving key: " + std::to_string(n) + " bases x " + std::to_string(PROVE_WIN) +
-                                  " window copies exceed the 2^31 window bases of one MSM");
-    DevBuf big;
-    big.ensure(asz * std::max<size_t>(n * PROVE_WIN, 1));
-    if (slot == MSM_H) {   // [IC | H]
-      const size_t nic = (size_t)pk.count[MSM_IC] + pk.extras[MSM_IC], nh = n - nic;
-      if (nic) ZK_HIP(hipMemcpyAsync(big.p, pk.bases[MSM_IC].p, asz * nic, hipMemcpyDeviceToDevice, st));
-      if (nh)
-        ZK_HIP(hipMemcpyAsync(static_cast<char*>(big.p) + asz * nic, pk.bases[MSM_H].p, asz * nh,
-                              hipMemcpyDeviceToDevice, st));
-      ZK_HIP(hipStreamSynchronize(st));
-      pk.bases[MSM_IC].release();
-    } else if (n) {
-      ZK_HIP(hipMemcpyAsync(big.p, pk.bases[slot].p, asz * n, hipMemcpyDeviceToDevice, st));
+    try {
+      pk_precompute_slot(ctx, pk, slot, PROVE_WIN_C, COPIES);
+    } catch (const Error& e) {
+      if (e.code != ZK_ERR_DEVICE || !pk.sound()) throw;
+      // most likely a key that does not fit: say which knob shrinks it
+      throw Error(ZK_ERR_DEVICE, std::string(e.what()) + " (a sound key holding " + std::to_string(COPIES) + " of " +
+                                     std::to_string(PROVE_WIN) +
+                                     " window copies of every base: ZK_OPT_SOUND_COPIES keeps fewer)");
     }
-    if (slot == MSM_B2) msm_precompute_windows<G2>(big.as<G2A>(), n, PROVE_WIN, PROVE_WIN_C, st);
-    else msm_precompute_windows<G1>(big.as<G1A>(), n, PROVE_WIN, PROVE_WIN_C, st);
-    ZK_HIP(hipStreamSynchronize(st));
-    pk.stride[slot] = slot == MSM_B2 ? msm_pad_bases<G2>(big, n * PROVE_WIN, st)
-                                     : msm_pad_bases<G1>(big, n * PROVE_WIN, st);
-    pk.bases[slot] = std::move(big);
   }
   pk.win = PROVE_WIN;
   pk.win_c = PROVE_WIN_C;
+  pk.copies = COPIES;
 }
 
 void pk_finish(zk_ctx* ctx, zk_pk_dev& pk, const zk_r1cs_csr* q, const std::vector<uint8_t>& own, hipStream_t st) {

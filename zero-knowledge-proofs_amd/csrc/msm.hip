@@ -71,6 +71,7 @@ MsmPlan msm_make_plan_shared(uint32_t n, int bits, int sw, int c) {
   const int top = bits - c * (p.nwin - 1);
   const int k = std::max(c - 1, top);   // signed digits <= 2^(c-1); the top window unsigned <= 2^top
   p.shared = 1;
+  p.copies = p.nwin;
   p.nred = 1;
   p.nb[0] = 1u << k;
   p.kr[0] = (uint8_t)(k / 2);
@@ -86,17 +87,12 @@ MsmPlan msm_make_plan_shared(uint32_t n, int bits, int sw, int c) {
   return p;
 }
 
-// Batch plan: segment k = one MSM with its own 2^k buckets [k 2^k, (k+1) 2^k)
-// and its own reduction window.
-static MsmPlan msm_make_plan_batch(const MsmSeg* segs, int nseg, int bits, int c) {
-  uint32_t total = 0;
-  for (int k = 0; k < nseg; k++) total += segs[k].n;
-  MsmPlan p = msm_make_plan_shared(total, bits, 1, c);
+// nsets copies of a shared plan's bucket set, each a reduction window of its
+// own: set k = buckets [k 2^kb, (k+1) 2^kb).
+static void plan_equal_sets(MsmPlan& p, int nsets) {
   const int kb = p.kr[0] + p.kc[0];
-  p.nseg = nseg;
-  p.nred = nseg;
-  p.segshift = kb;
-  for (int k = 0; k < nseg; k++) {
+  p.nred = nsets;
+  for (int k = 0; k < nsets; k++) {
     p.nb[k] = 1u << kb;
     p.kr[k] = p.kr[0];
     p.kc[k] = p.kc[0];
@@ -104,9 +100,34 @@ static MsmPlan msm_make_plan_batch(const MsmSeg* segs, int nseg, int bits, int c
     p.rcoff[k] = k * ((1u << p.kr[0]) + (1u << p.kc[0]));
     p.qoff[k] = k * (p.kr[0] + p.kc[0] + 1);
   }
-  p.boff[nseg] = p.G = (uint32_t)nseg << kb;
-  p.rcoff[nseg] = p.nrc = nseg * ((1u << p.kr[0]) + (1u << p.kc[0]));
-  p.qoff[nseg] = p.nq = nseg * (p.kr[0] + p.kc[0] + 1);
+  p.boff[nsets] = p.G = (uint32_t)nsets << kb;
+  p.rcoff[nsets] = p.nrc = nsets * ((1u << p.kr[0]) + (1u << p.kc[0]));
+  p.qoff[nsets] = p.nq = nsets * (p.kr[0] + p.kc[0] + 1);
+}
+
+// Batch plan: segment k = one MSM with its own 2^k buckets [k 2^k, (k+1) 2^k)
+// and its own reduction window.
+static MsmPlan msm_make_plan_batch(const MsmSeg* segs, int nseg, int bits, int c) {
+  uint32_t total = 0;
+  for (int k = 0; k < nseg; k++) total += segs[k].n;
+  MsmPlan p = msm_make_plan_shared(total, bits, 1, c);
+  p.nseg = nseg;
+  p.segshift = p.kr[0] + p.kc[0];
+  plan_equal_sets(p, nseg);
+  return p;
+}
+
+// One MSM whose windows go S at a time into R = ceil(W / S) bucket sets
+// (msm.hpp).  The buckets still belong to one MSM (nseg = 1, segshift 31);
+// the last set is only partly used when S does not divide W.
+MsmPlan msm_make_plan_grouped(uint32_t n, int bits, int sw, int c, int copies) {
+  MsmPlan p = msm_make_plan_shared(n, bits, sw, c);
+  if (copies <= 0 || copies >= p.nwin) return p;
+  const int sets = (p.nwin + copies - 1) / copies;
+  if (sets > MSM_MAXWIN || ((uint64_t)sets << (p.kr[0] + p.kc[0])) >= 0x80000000ull)
+    throw Error(ZK_ERR_ARG, "msm: too many bucket sets");
+  p.copies = copies;
+  plan_equal_sets(p, sets);
   return p;
 }
 
@@ -919,10 +940,11 @@ void msm_launch(MsmWork& w, const typename C::A* d_bases, const uint64_t* d_scal
 }
 
 template <class C>
-void msm_launch_shared(MsmWork& w, const typename C::A* d_bases, const uint64_t* d_scalars, int sw, uint32_t n,
-                       int bits, int c, hipStream_t st, uint32_t stride) {
-  w.plan = msm_make_plan_shared(n, bits, sw, c);
-  if ((uint64_t)n * w.plan.nwin >= MSM_DUMMY) throw Error(ZK_ERR_ARG, "msm: too many window bases");
+void msm_launch_grouped(MsmWork& w, const typename C::A* d_bases, const uint64_t* d_scalars, int sw, uint32_t n,
+                        int bits, int c, int copies, hipStream_t st, uint32_t stride) {
+  w.plan = msm_make_plan_grouped(n, bits, sw, c, copies);
+  // an entry indexes copy j's base i as j n + i in 31 bits
+  if ((uint64_t)n * w.plan.copies >= MSM_DUMMY) throw Error(ZK_ERR_ARG, "msm: too many window bases");
   const MsmSeg seg{d_bases, d_scalars, n, stride};
   msm_front_impl<C>(w, &seg, 1, sw, st);
   msm_back_impl<C>(w, st, MSM_BACK_FULL, nullptr);
@@ -1079,8 +1101,10 @@ static host::X<typename C::HF> msm_finish_impl(const MsmWork& w, int seg) {
   const HX* r = w.host_res.as<const HX>();
   // reduction window `win` carries weight 2^(c win); a shared plan has one
   // window of weight 1 (the shifts live in the precomputed bases), a batch
-  // one window of weight 1 per MSM
-  auto wexp = [&](int win) { return p.shared ? 0 : p.c * win; };
+  // one window of weight 1 per MSM, a grouped plan bucket set `win` of weight
+  // 2^(c S win): the S windows of a set differ by the shifts of the copies,
+  // set to set by S whole windows
+  auto wexp = [&](int win) { return !p.shared ? p.c * win : p.nseg > 1 ? 0 : p.c * p.copies * win; };
   const int w0 = seg < 0 ? 0 : seg, w1 = seg < 0 ? (int)p.nred : seg + 1;
   int maxe = 0;
   for (int win = w0; win < w1; win++)
@@ -1190,8 +1214,8 @@ void host_to_abi<G2>(const host::X<host::Fq2>& p, uint64_t* w) {
 #define ZK_MSM_INST(C)                                                                               \
   template void msm_launch<C>(MsmWork&, const C::A*, const uint64_t*, int, uint32_t, int, hipStream_t,  \
                               uint32_t);                                                              \
-  template void msm_launch_shared<C>(MsmWork&, const C::A*, const uint64_t*, int, uint32_t, int, int,   \
-                                     hipStream_t, uint32_t);                                          \
+  template void msm_launch_grouped<C>(MsmWork&, const C::A*, const uint64_t*, int, uint32_t, int, int,  \
+                                      int, hipStream_t, uint32_t);                                    \
   template uint32_t msm_pad_bases<C>(DevBuf&, size_t, hipStream_t);                                  \
   template void msm_precompute_windows<C>(C::A*, size_t, int, int, hipStream_t);                       \
   template void batch_normalize<C>(const C::X*, size_t, C::F*, C::A*, hipStream_t);                    \

@@ -86,7 +86,8 @@ struct MsmPlan {
   uint32_t rcoff[MSM_MAXWIN + 1];   // first row/col partial sum of window w (rows, then columns)
   uint32_t qoff[MSM_MAXWIN + 1];    // first quantity of window w (U^C, U^D, P)
   uint32_t nred;                    // reduction windows (nwin, or 1 when shared, or nseg)
-  int shared;                       // windows share one bucket set (precomputed 2^(c w) P bases)
+  int shared;                       // windows share bucket sets (precomputed 2^(c w) P bases)
+  int copies;                       // shared: base copies S; window w reads copy w mod S into set w / S
   int nseg;                         // batch: independent MSMs, reduction window k = MSM k
   uint32_t segshift;                // batch: bucket g belongs to MSM g >> segshift
   int all_valid;                    // every bucket holds a value (msm_batch_back COMBINE wrote them all)
@@ -121,6 +122,14 @@ void msm_offsets(MsmWork& w, uint32_t M, hipStream_t st);
 // ONE set of 2^max(c-1, top) buckets -- the bucket reduction shrinks by the
 // window count and the per-window Horner disappears.
 MsmPlan msm_make_plan_shared(uint32_t n, int bits, int sw, int c);
+// Grouped-window plan: only the first S = min(copies, W) shifted copies
+// 2^(c j) P_i, j < S, are kept (copies <= 0: all W, the shared plan).  Digit
+// window w reads copy w mod S and accumulates into bucket set w / S; the
+// R = ceil(W / S) equal sets (laid out like a batch's: set t from bucket
+// t << k) are R reduction windows, set t of weight 2^(c S t) in the host
+// tail.  S = W is the shared plan, S = 1 the per-window plan over the bases
+// as they are -- the memory of the copies against R bucket reductions.
+MsmPlan msm_make_plan_grouped(uint32_t n, int bits, int sw, int c, int copies);
 
 // Device workspace of one in-flight MSM.
 struct MsmWork {
@@ -139,10 +148,12 @@ struct MsmWork {
 template <class C>
 void msm_launch(MsmWork& w, const typename C::A* d_bases, const uint64_t* d_scalars, int sw,
                 uint32_t n, int bits, hipStream_t st, uint32_t stride = 0);
-// Same over window-shifted bases: d_bases holds nwin x n points, window-major.
+// Same over window-shifted bases: d_bases holds the first `copies` shifted
+// copies, copies x n points, copy-major (msm_make_plan_grouped).  copies <= 0
+// or >= the window count: every copy, one bucket set (the shared plan).
 template <class C>
-void msm_launch_shared(MsmWork& w, const typename C::A* d_bases, const uint64_t* d_scalars, int sw,
-                       uint32_t n, int bits, int c, hipStream_t st, uint32_t stride = 0);
+void msm_launch_grouped(MsmWork& w, const typename C::A* d_bases, const uint64_t* d_scalars, int sw,
+                        uint32_t n, int bits, int c, int copies, hipStream_t st, uint32_t stride = 0);
 // Up to MSM_MAXSEG independent MSMs over window-shifted bases with 64-bit
 // scalars, run as ONE key pass / sort / accumulate / merge / bucket
 // reduction: MSM k owns buckets [k 2^s, (k+1) 2^s).  The latency-bound
@@ -164,7 +175,8 @@ void msm_batch_front(MsmWork& w, const MsmSeg* segs, int nseg, int bits, int c, 
 template <class C>
 void msm_batch_back(MsmWork& w, hipStream_t st, int mode, const MsmWork* prev);
 // d_bases[w n + i] = 2^(c w) d_bases[i] for 0 < w < W (the first n are given;
-// capacity W n).  One-time, at proving-key upload.
+// capacity W n).  One-time, at proving-key upload.  A grouped plan asks for
+// its S copies only (W = S).
 template <class C>
 void msm_precompute_windows(typename C::A* d_bases, size_t n, int W, int c, hipStream_t st);
 // Base gathers by the accumulate are random: a packed 96-B G1 point straddles

@@ -323,7 +323,7 @@ struct ProveRun {
   const hipStream_t s_g2, s_abi;
   // A sound key: every scalar whole (sw = 4 words, 255 bits) instead of its
   // lo64, over the key's ceil(255 / c) window copies, and A, B1 and IC+H each
-  // an MSM of its own (msm_launch_shared) on the same streams; the witness is
+  // an MSM of its own (msm_launch_grouped) on the same streams; the witness is
   // whole on the device before the first kernel (no split upload).
   const bool sound;
   const int sw, bits;
@@ -443,14 +443,15 @@ struct ProveRun {
       ZK_LAUNCH_CHECK();
     }
   }
-  // One MSM of a sound key over the slot's window copies (MSM_H: [IC | H]), downloaded
+  // One MSM of a sound key over the slot's window copies (MSM_H: [IC | H]; all of
+  // them, or the grouped-window plan over those the key kept), downloaded
   template <class C>
   void launch_shared(int slot, const char* tag, hipStream_t gs) {
     MsmWork& w = ctx->msm[slot];
     w.tag = serial ? tag : "";
     const uint32_t n = slot == MSM_H ? pk->ich_tot() : pk->count[slot] + pk->extras[slot];
-    msm_launch_shared<C>(w, pk->bases[slot].as<typename C::A>(), scal(slot), sw, n, bits, pk->win_c, gs,
-                         pk->stride[slot]);
+    msm_launch_grouped<C>(w, pk->bases[slot].as<typename C::A>(), scal(slot), sw, n, bits, pk->win_c, pk->copies, gs,
+                          pk->stride[slot]);
     msm_download<C>(w, gs);
   }
   // n points from compacted position lo of a slot's window-shifted bases (MSM_H: the [IC | H] vector)
@@ -529,8 +530,8 @@ struct ProveRun {
       MsmWork& w = ctx->msm[MSM_B2];
       w.tag = serial ? "B2/" : "";
       gather(MSM_B2, 0, pk->count[MSM_B2], true, s_g2);
-      msm_launch_shared<G2>(w, pk->bases[MSM_B2].as<G2A>(), scal(MSM_B2), sw, pk->count[MSM_B2] + pk->extras[MSM_B2],
-                            bits, pk->win_c, s_g2, pk->stride[MSM_B2]);
+      msm_launch_grouped<G2>(w, pk->bases[MSM_B2].as<G2A>(), scal(MSM_B2), sw, pk->count[MSM_B2] + pk->extras[MSM_B2],
+                             bits, pk->win_c, pk->copies, s_g2, pk->stride[MSM_B2]);
       msm_download<G2>(w, s_g2);
       ZK_HIP(hipEventRecord(ctx->ev_done[MSM_B2], s_g2));
     }

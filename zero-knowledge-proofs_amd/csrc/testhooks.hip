@@ -65,7 +65,7 @@ int zk_test_fault_after_exchange(zk_ctx* ctx, int k) {
 
 int zk_test_pk_bases(zk_ctx* ctx, const zk_pk_dev* pk, int slot, int window, uint32_t* idx_out, uint64_t* words_out,
                      size_t cap, size_t* count, size_t* nextras) {
-  if (!ctx || !pk || !count || !nextras || slot < 0 || slot >= NUM_MSM || window < 0 || window >= pk->win)
+  if (!ctx || !pk || !count || !nextras || slot < 0 || slot >= NUM_MSM || window < 0 || window >= pk->copies)
     return ZK_ERR_ARG;
   const size_t cnt = pk->count[slot], nex = pk->extras[slot], tot = cnt + nex;
   *count = cnt;
@@ -282,5 +282,12 @@ int zk_test_pk_info(const zk_pk_dev* pk,uint32_t* win, uint32_t* win_c, uint32_t
   *win_c = (uint32_t)pk->win_c;
   *shard = pk->shard;
   *nshards = pk->nshards;
+  return ZK_OK;
+}
+
+int zk_test_pk_plan(const zk_pk_dev* pk, uint32_t* copies, uint32_t* sets) {
+  if (!pk || !copies || !sets) return ZK_ERR_ARG;
+  *copies = (uint32_t)pk->copies;
+  *sets = (uint32_t)((pk->win + pk->copies - 1) / pk->copies);
   return ZK_OK;
 }

@@ -204,6 +204,48 @@ def test_prove_equals_the_reference(zkp, ctx, case, qap4):
     assert zkp.Verifier.verify(vk, zkp.Proof.deserialize_compressed(want), [case["z"][1]])
 
 
+@pytest.mark.parametrize("removed", ["middle", "trailing"])
+def test_prove_with_identity_h_bases(zkp, ctx, pyref, case, qap4, removed):
+    """The whole-scalar twin of test_gpu_prove.py's test of the same name: the
+    two ways H reaches the IC+H scalar vector, four words a scalar.  A sound
+    setup never makes an identity h_g1 entry, so the reference key gets one by
+    hand.  middle: index 1 -- the compacted H index is no longer the position
+    (h_ident false), the quotient writes to its own buffer and a gather at
+    offset count[IC] follows.  trailing: the last index with a non-zero
+    coefficient, and the entry after it, whose coefficient is zero (n = 4: H
+    has n - 1 coefficients, h_g1 n entries), so that the identity entries end
+    the vector and only shorten it (h_ident true, count[H] < n): the quotient
+    writes straight into the scalar vector.  Host and device witness, both
+    quotient paths, against sound_ref.prove_sound on the same modified key."""
+    n = sound_ref.CASE_N
+    h = case["qap"].compute_quotient_polynomial(case["z"])
+    last = max(i for i, c in enumerate(h) if c % R)
+    gone = [1] if removed == "middle" else list(range(last, n))
+    assert h[gone[0]] % R and not any(h[i] % R for i in gone[1:] if i < len(h))
+    pk = dict(case["pk"])
+    pk["h_g1"] = [pyref.INF if i in gone else p for i, p in enumerate(case["pk"]["h_g1"])]
+    proof = sound_ref.prove_sound(pk, case["qap"], case["z"], sound_ref.CASE_PUBLIC, case["r"], case["s"])
+    assert proof[2] != case["proof"][2] and proof[:2] == case["proof"][:2]   # the removed base carried a coefficient
+    want = sound_ref.proof_to_product(zkp, proof).serialize_compressed()
+    assert want != sound_ref.proof_to_product(zkp, case["proof"]).serialize_compressed()
+    w = zkp.Witness(case["z"], sound_ref.CASE_PUBLIC)
+    dz = _device_z(w.assignment)
+    dpk = sound_ref.pk_to_product(zkp, pk, qap4).upload(ctx)
+    try:
+        assert dpk.sound
+        idx, _, _ = dpk.test_bases(SLOT_H)
+        assert len(idx) == n - len(gone)
+        assert np.array_equal(idx, np.arange(len(idx))) == (removed == "trailing")
+        for path in (0, 1):
+            ctx.set_option(zkp.ZK_OPT_QUOTIENT_PATH, path)
+            assert zkp.Prover.prove(dpk, w, r=case["r"], s=case["s"]).serialize_compressed() == want, path
+            got = zkp.Prover.prove_device(dpk, dz.data_ptr(), len(w.assignment), sound_ref.CASE_PUBLIC, case["r"],
+                                          case["s"])
+            assert got.serialize_compressed() == want, path
+    finally:
+        dpk.free()
+
+
 def test_reference_toy_verifies_in_sound_mode(zkp, ctx):
     """x * y = z, z = [1, 3, 4, 12], the full-width parameter set that
     test_gpu_prove.py::test_gpu_proof_verifies_when_untruncated expects to

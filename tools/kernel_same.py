@@ -1,9 +1,10 @@
 """Compare the MSM kernels of two device assembly files, kernel by kernel.
 
     hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S msm.hip -o X.s   (both trees)
-    python3 tools/kernel_same.py OLD.s NEW.s
+    python3 tools/kernel_same.py OLD.s NEW.s [scalar_width]
 
-A kernel's body is the text between its label and its .Lfunc_end.  Before
+(scalar_width: the prove / setup / dist kernels of SCALAR_WIDTH_MAP below
+instead of the MSM ones.)  A kernel's body is the text between its label and its .Lfunc_end.  Before
 comparing, comments, directives and blank lines are dropped, block labels
 (.LBB<function>_<block>) and .Lpost_getpc<n> lose the numbering that depends
 on the function's place in the file, and symbols that carry a kernel's name
@@ -31,6 +32,25 @@ NAME_MAP = [
     ("_ZN2zk11k_msm_mergeINS_2G2E", "_ZN2zk11k_msm_mergeINS_2G2E"),
 ]
 
+# `python3 tools/kernel_same.py OLD.s NEW.s scalar_width`, each side the
+# concatenated assembly of prove.hip, setup.hip, dist.hip and ntt.hip: the
+# lo64 / whole-scalar twins became the <1> / <4> instances of one template over
+# the scalar width.  Every kernel whose name did not change is compared too.
+SCALAR_WIDTH_MAP = [
+    ("_ZN2zk9k_h_finalE", "_ZN2zk9k_h_finalILi1EE"),
+    ("_ZN2zk14k_h_final_fullE", "_ZN2zk9k_h_finalILi4EE"),
+    ("_ZN2zk8k_h_lo64E", "_ZN2zk12k_fr_scalarsILi1EE"),
+    ("_ZN2zk6k_lo64E", "_ZN2zk12k_fr_scalarsILi1EE"),
+    ("_ZN2zk9k_h_canonE", "_ZN2zk12k_fr_scalarsILi4EE"),
+    ("_ZN2zk11k_from_montE", "_ZN2zk12k_fr_scalarsILi4EE"),
+    ("_ZN2zk13k_gather_lo64E", "_ZN2zk8k_gatherILi1EE"),
+    ("_ZN2zk11k_gather_frE", "_ZN2zk8k_gatherILi4EE"),
+    ("_ZN2zk15k_setup_scalarsE", "_ZN2zk15k_setup_scalarsILi1EE"),
+    ("_ZN2zk20k_setup_scalars_fullE", "_ZN2zk15k_setup_scalarsILi4EE"),
+    ("_ZN2zk12k_set_extrasE", "_ZN2zk12k_set_extrasE"),
+    ("_ZN2zk15k_set_extras_frE", "_ZN2zk12k_set_extrasE"),
+]
+
 
 def kernels(path):
     """{mangled name: normalised instruction lines} of every function in the file."""
@@ -51,7 +71,7 @@ def kernels(path):
             continue   # comment, blank, directive
         line = re.sub(r"\.LBB\d+_", ".LBB_", line)
         line = re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", line)
-        line = re.sub(r"_Z\w*k_msm_\w*", "KSYM", line)
+        line = re.sub(r"_ZN2zk\d+k_\w*", "KSYM", line)
         body.append(line)
     return out
 
@@ -63,8 +83,13 @@ def find(ks, prefix):
 
 def main():
     old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+    pairs = NAME_MAP
+    if len(sys.argv) > 3 and sys.argv[3] == "scalar_width":
+        mapped = {p for p, _ in SCALAR_WIDTH_MAP}
+        pairs = SCALAR_WIDTH_MAP + [(k, k) for k in old if k in new and re.match(r"_ZN2zk\d+k_", k)
+                                    and not any(k.startswith(p) for p in mapped)]
     bad = 0
-    for po, pn in NAME_MAP:
+    for po, pn in pairs:
         ko, kn = find(old, po), find(new, pn)
         if ko is None or kn is None:
             print(f"missing    {po} -> {pn}")

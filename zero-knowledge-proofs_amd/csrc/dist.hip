@@ -178,8 +178,7 @@ __global__ void __launch_bounds__(256) k_dq_h(const Fr* __restrict__ hb, const F
   const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (d >= m) return;
   const uint64_t p = log_m ? (__builtin_bitreverse32((uint32_t)d) >> (32 - log_m)) : 0;
-  const Fr h = fp_from_mont(fp_mul(ld_vec(&hb[p]), ld_vec(&gipow[rank + (uint64_t)world * d])));
-  hlo[d] = (uint64_t)h.v[0] | ((uint64_t)h.v[1] << 32);   // core:203-208
+  st_scal<1>(hlo, d, fp_mul(ld_vec(&hb[p]), ld_vec(&gipow[rank + (uint64_t)world * d])));   // a sharded key: lo64
 }
 
 // ------------------------------------------------------------- driver ---

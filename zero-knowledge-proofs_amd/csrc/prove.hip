@@ -70,66 +70,67 @@ __device__ __forceinline__ uint32_t brev(uint32_t x, uint32_t log_n) {
   return log_n ? (__builtin_bitreverse32(x) >> (32 - log_n)) : 0;
 }
 
-// H_i = n^-1 g^-i * (bit-reversed iNTT output)[i], then lo64 (core:203-208):
-// the element-wise gather path for domains that stay in the MALL
+// The kernels below write MSM scalars of SW u64 words: 1, the lo64 of the
+// reference (core:156-161, 203-208), or 4, whole, for a sound key
+// (zk_pk_dev::sound).  st_scal<SW> (quotient.hpp) is the only difference.
+//
+// H_i = n^-1 g^-i * (bit-reversed iNTT output)[i] as a scalar: the
+// element-wise gather path for domains that stay in the MALL
+template <int SW>
 __global__ void __launch_bounds__(256) k_h_final(const Fr* __restrict__ hb, const Fr* __restrict__ gipow,
-                                                 uint32_t log_n, uint64_t* __restrict__ hlo) {
+                                                 uint32_t log_n, uint64_t* __restrict__ h) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >> log_n) return;
-  Fr h = fp_from_mont(fp_mul(ld_vec(&hb[brev((uint32_t)i, log_n)]), ld_vec(&gipow[i])));
-  hlo[i] = (uint64_t)h.v[0] | ((uint64_t)h.v[1] << 32);
+  st_scal<SW>(h, i, fp_mul(ld_vec(&hb[brev((uint32_t)i, log_n)]), ld_vec(&gipow[i])));
+}
+static void h_final(const Fr* hb, const Fr* gipow, uint32_t log_n, int sw, uint64_t* h, hipStream_t st) {
+  const uint32_t nb = ceil_div((size_t)1 << log_n, 256);
+  if (sw == 1) k_h_final<1><<<nb, 256, 0, st>>>(hb, gipow, log_n, h);
+  else k_h_final<4><<<nb, 256, 0, st>>>(hb, gipow, log_n, h);
+  ZK_LAUNCH_CHECK();
 }
 
-// H_i (Montgomery, natural order, n^-1 g^-i already applied) -> lo64 of the
-// canonical value (core:203-208)
-__global__ void __launch_bounds__(256) k_h_lo64(const Fr* __restrict__ h, size_t n, uint64_t* __restrict__ hlo) {
+// n Montgomery Fr -> scalars (the quotient's natural-order path, where
+// n^-1 g^-i is already applied; setup's tau powers)
+template <int SW>
+__global__ void __launch_bounds__(256) k_fr_scalars(const Fr* __restrict__ in, size_t n, uint64_t* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const Fr c = fp_from_mont(ld_vec(&h[i]));
-  hlo[i] = (uint64_t)c.v[0] | ((uint64_t)c.v[1] << 32);
+  if (i < n) st_scal<SW>(out, i, ld_vec(&in[i]));
+}
+void fr_to_scalars(const Fr* d_in, size_t n, int sw, uint64_t* d_out, hipStream_t st) {
+  if (!n) return;
+  if (sw == 1) k_fr_scalars<1><<<ceil_div(n, 256), 256, 0, st>>>(d_in, n, d_out);
+  else k_fr_scalars<4><<<ceil_div(n, 256), 256, 0, st>>>(d_in, n, d_out);
+  ZK_LAUNCH_CHECK();
 }
 
-// out[k] = low word of src[idx[k] / div] (div > 1: a distributed-quotient
-// rank holds H_(rank + div d) at position d)
-__global__ void __launch_bounds__(256) k_gather_lo64(const uint64_t* __restrict__ src, int stride_words,
-                                                     const uint32_t* __restrict__ idx, uint32_t div,
-                                                     uint32_t count, uint64_t* __restrict__ out) {
+// out[k] = scalar idx[k] / div of src (canonical).  SW = 1: its low word, the
+// scalars stride_words apart (4: a witness, 1: lo64(H)); div > 1: a
+// distributed-quotient rank holds H_(rank + div d) at position d.  SW = 4:
+// whole canonical Fr; a sound key is never sharded (div = 1).
+template <int SW>
+__global__ void __launch_bounds__(256) k_gather(const uint64_t* __restrict__ src, int stride_words,
+                                                const uint32_t* __restrict__ idx, uint32_t div, uint32_t count,
+                                                uint64_t* __restrict__ out) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= count) return;
-  out[k] = src[(size_t)(idx[k] / div) * stride_words];
+  if constexpr (SW == 1) out[k] = src[(size_t)(idx[k] / div) * stride_words];
+  else st_vec(reinterpret_cast<Fr*>(out) + k, ld_vec(reinterpret_cast<const Fr*>(src) + idx[k]));
+}
+static void gather_scalars(const uint64_t* src, int stride_words, const uint32_t* idx, uint32_t div, uint32_t count,
+                           int sw, uint64_t* out, hipStream_t st) {
+  if (!count) return;
+  if (sw == 1) k_gather<1><<<ceil_div(count, 256), 256, 0, st>>>(src, stride_words, idx, div, count, out);
+  else k_gather<4><<<ceil_div(count, 256), 256, 0, st>>>(src, stride_words, idx, div, count, out);
+  ZK_LAUNCH_CHECK();
 }
 
+// an MSM's extras' scalars: 1, then r or s -- as five one-word scalars
+// [1, r0..r3], or as two whole ones [1,0,0,0, r0..r3]
 struct Extras {
-  uint64_t v[5];
+  uint64_t v[8];
 };
-__global__ void k_set_extras(uint64_t* __restrict__ dst, Extras e, uint32_t n) {
-  if (threadIdx.x < n) dst[threadIdx.x] = e.v[threadIdx.x];
-}
-
-// ---- a sound key (zk_pk_dev::sound): the same scalars whole, 4 words each ----
-// k_h_final / k_h_lo64 without the truncation: canonical H_i
-__global__ void __launch_bounds__(256) k_h_final_full(const Fr* __restrict__ hb, const Fr* __restrict__ gipow,
-                                                      uint32_t log_n, Fr* __restrict__ h) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >> log_n) return;
-  st_vec(&h[i], fp_from_mont(fp_mul(ld_vec(&hb[brev((uint32_t)i, log_n)]), ld_vec(&gipow[i]))));
-}
-__global__ void __launch_bounds__(256) k_h_canon(const Fr* __restrict__ h, size_t n, Fr* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  st_vec(&out[i], fp_from_mont(ld_vec(&h[i])));
-}
-// out[k] = src[idx[k]], whole canonical Fr
-__global__ void __launch_bounds__(256) k_gather_fr(const Fr* __restrict__ src, const uint32_t* __restrict__ idx,
-                                                   uint32_t count, Fr* __restrict__ out) {
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= count) return;
-  st_vec(&out[k], ld_vec(&src[idx[k]]));
-}
-struct ExtrasFr {
-  uint64_t v[8];   // two whole scalars: 1, then r or s
-};
-__global__ void k_set_extras_fr(uint64_t* __restrict__ dst, ExtrasFr e, uint32_t nwords) {
+__global__ void k_set_extras(uint64_t* __restrict__ dst, Extras e, uint32_t nwords) {
   if (threadIdx.x < nwords) dst[threadIdx.x] = e.v[threadIdx.x];
 }
 
@@ -167,11 +168,10 @@ struct Partial {
 };
 static_assert(sizeof(Partial) <= ZK_PARTIAL_BYTES, "partial size");
 
-// h_out: lo64(H_i), one word per coefficient; for a sound key the whole
-// canonical H_i, four words each
-static void quotient(zk_ctx* ctx, const zk_pk_dev* pk, const uint64_t* d_z, hipStream_t st, uint64_t* h_out) {
+// h_out: H_i as scalars of sw words per coefficient (1: lo64(H_i), 4: the
+// whole canonical H_i)
+static void quotient(zk_ctx* ctx, const zk_pk_dev* pk, const uint64_t* d_z, int sw, hipStream_t st, uint64_t* h_out) {
   const uint64_t n = pk->n;
-  const bool full = pk->sound();
   NttDomain& dom = ctx->domain(pk->log_n);
   ctx->qabc.ensure(sizeof(Fr) * 3 * n);
   Fr* v[3] = {ctx->qabc.as<Fr>(), ctx->qabc.as<Fr>() + n, ctx->qabc.as<Fr>() + 2 * n};
@@ -215,16 +215,11 @@ static void quotient(zk_ctx* ctx, const zk_pk_dev* pk, const uint64_t* d_z, hipS
   // natural order (the bit reversal is the first pass's tiled gather,
   // n^-1 g^-i fused into the last pass's store) into v[1], v[2] as scratch,
   // since beyond the MALL every gathered 32-B element was its own line/page
-  ctx->tmp_scal.ensure(sizeof(uint64_t) * (full ? 4 : 1) * n);
+  ctx->tmp_scal.ensure(sizeof(uint64_t) * sw * n);
   if (!large) {
     ntt_dif(v[0], dom, true, st, pf);
     ph = pf->begin(st, "quotient_misc", n);
-    if (full)
-      k_h_final_full<<<ceil_div(n, 256), 256, 0, st>>>(v[0], domain_gipow(dom, st), pk->log_n,
-                                                       reinterpret_cast<Fr*>(h_out));
-    else
-      k_h_final<<<ceil_div(n, 256), 256, 0, st>>>(v[0], domain_gipow(dom, st), pk->log_n, h_out);
-    ZK_LAUNCH_CHECK();
+    h_final(v[0], domain_gipow(dom, st), pk->log_n, sw, h_out, st);
     pf->end(st, ph);
     return;
   }
@@ -236,9 +231,7 @@ static void quotient(zk_ctx* ctx, const zk_pk_dev* pk, const uint64_t* d_z, hipS
     ntt_natural(v[1], v[0], v[2], dom, true, st, pf, nullptr, domain_gipow(dom, st), nullptr);
   }
   ph = pf->begin(st, "quotient_misc", n);
-  if (full) k_h_canon<<<ceil_div(n, 256), 256, 0, st>>>(h, n, reinterpret_cast<Fr*>(h_out));
-  else k_h_lo64<<<ceil_div(n, 256), 256, 0, st>>>(h, n, h_out);
-  ZK_LAUNCH_CHECK();
+  fr_to_scalars(h, n, sw, h_out, st);
   pf->end(st, ph);
 }
 
@@ -265,17 +258,22 @@ static int status_from_flags(uint32_t flags) {
   return ZK_OK;
 }
 
-// The G1 MSMs run as two pipelines (msm_launch_batch: one sort, accumulate,
-// merge and bucket reduction each, so the latency-bound tails cost one tree
-// depth per pipeline): A and B1, a batch of two MSMs that need only z, start
-// with the witness; IC and H -- both terms of pi_C = IC + H_1 + s pi_A +
-// r B_1 (core:224-265), so ONE MSM over the bases [ic_g1 | h_g1] with the
-// scalars [lo64(z_i) | lo64(H_i)] -- follows the quotient.  One bucket set
-// for IC and H: a bucket reduction fewer per proof than IC in the first batch
-// and H alone.
+// The G1 MSMs run as two groups: A and B1, which need only z, start with the
+// witness; IC and H -- both terms of pi_C = IC + H_1 + s pi_A + r B_1
+// (core:224-265), so ONE MSM over the bases [ic_g1 | h_g1] with the scalars
+// [z_i | H_i] -- follows the quotient.  One bucket set for IC and H: a bucket
+// reduction fewer per proof than IC in the first group and H alone.
+// The key's mode enters as sw, the u64 words of a scalar: 1 (lo64, the
+// reference) or 4 (whole, a sound key), with the key's scalar_bits and window
+// copies.  The same groups on the same streams either way; how a group's
+// slots become MSMs -- at sw = 1 one batch (msm_launch_batch: one sort,
+// accumulate, merge and bucket reduction, so the latency-bound tails cost one
+// tree depth per group) -- is ProveRun::launch_g1's decision alone.
 static const int G1_AB[2] = {MSM_A, MSM_B1};
 static const int G2_B[1] = {MSM_B2}, G1_ICH[1] = {MSM_H};
-static const int WAITS[3] = {MSM_B2, MSM_A, MSM_H};   // MSM_A: the A+B1 batch, MSM_H: IC + H
+static const int WAITS[3] = {MSM_B2, MSM_A, MSM_H};   // MSM_A: the A + B1 group, MSM_H: IC + H
+// per-MSM profiling prefixes of the slots (MSM_H: [IC | H]); "AB/": A + B1 as one batch
+static const char* const SLOT_TAG[5] = {"A/", "B2/", "B1/", "IC/", "ICH/"};
 
 // What one shard's proof is made from, beside the key, r and s: the device witness d_z, and
 // h_given (virtual-rank tests): this shard's lo64(H_(shard + nshards d)) is
@@ -315,17 +313,14 @@ struct ProveRun {
   const hipStream_t st;
   const bool split;   // a host witness, uploaded in parts
   // Streams (<= GPU_MAX_HW_QUEUES = 4, so no two share a hardware queue):
-  // main (high priority) runs the quotient and then the H batch that depends
-  // on it; side[0] (high) the G2 MSM, the longest chain; side[1] the A+B1+IC
-  // batch.  The latency-bound phases of one MSM overlap the throughput-bound
+  // main (high priority) runs the quotient and then the IC+H group that
+  // depends on it; side[0] (high) the G2 MSM, the longest chain; side[1] the
+  // A + B1 group and IC's gather.  The latency-bound phases of one MSM overlap the throughput-bound
   // accumulation of another.  Schedule 3 runs everything in order on main.
   const bool serial;
   const hipStream_t s_g2, s_abi;
-  // A sound key: every scalar whole (sw = 4 words, 255 bits) instead of its
-  // lo64, over the key's ceil(255 / c) window copies, and A, B1 and IC+H each
-  // an MSM of its own (msm_launch_grouped) on the same streams; the witness is
-  // whole on the device before the first kernel (no split upload).
-  const bool sound;
+  // u64 words and bits of every scalar: 1 and 64 (its lo64), or 4 and 255 for
+  // a sound key (whole, over the key's window copies)
   const int sw, bits;
   // The quotient: local (every coefficient), distributed over the ranks of
   // a sharded key (this rank's coefficients i = shard mod N), or given
@@ -333,7 +328,7 @@ struct ProveRun {
   const bool dist;
   const uint64_t* h_src;
   const uint32_t h_div;
-  // IC+H scalars: [nic lo64(z_i) | lo64(H_i)], H's straight from the quotient when h_direct
+  // IC+H scalars: [nic z_i | H_i], sw words each, H's straight from the quotient when h_direct
   const uint32_t nic;
   const bool h_direct;
   // IC's scalars need only z: gathered ahead of the quotient on the A+B1
@@ -346,9 +341,13 @@ struct ProveRun {
   ProveRun(zk_ctx* c, const zk_pk_dev* k, const zk_fr* r_, const zk_fr* s_, const ProveInput& i)
       : ctx(c), pk(k), r(r_), s(s_), in(i), st(c->stream), split(i.z_host != nullptr), serial(c->sched == 3),
         s_g2(serial ? st : c->side[0]), s_abi(serial ? st : c->side[1]),
-        sound(k->sound()), sw(k->sound() ? 4 : 1), bits((int)k->scalar_bits),        dist(!i.h_given && uses_dist_quotient(c, k)),
+        sw(k->sound() ? 4 : 1), bits((int)k->scalar_bits), dist(!i.h_given && uses_dist_quotient(c, k)),
         h_src(i.h_given ? i.h_given : c->tmp_scal.as<uint64_t>()), h_div((i.h_given || dist) ? k->nshards : 1),
-        nic(k->count[MSM_IC]), h_direct(k->h_ident && !dist && !i.h_given) {}
+        nic(k->count[MSM_IC]), h_direct(k->h_ident && !dist && !i.h_given) {
+    // the split upload's parts are batches of one-word scalars (launch_part):
+    // prove_impl sends a sound key's host witness up whole instead
+    if (split && sw != 1) throw Error(ZK_ERR_ARG, "a split witness upload needs a reference-mode key");
+  }
 
   uint32_t* flags() const { return ctx->flags.as<uint32_t>(); }
   uint64_t* scal(int slot) const { return ctx->scal[slot].as<uint64_t>(); }
@@ -379,50 +378,29 @@ struct ProveRun {
     ZK_HIP(hipEventRecord(ctx->ev_scal, st));                     // z (and flags reset) ready
   }
 
-  // ---- scalars of one MSM: lo64 of its variables (or H coefficients), then
-  // the extras' scalars (1 for alpha_1 / beta_2 / beta_1, the u64 limbs of r or s)
+  // ---- scalars of one MSM, sw words each: its variables' z (or H
+  // coefficients), then the extras' scalars: 1 for alpha_1 / beta_2 / beta_1,
+  // then r (delta_1) or s (delta_2) -- at sw = 1 its four u64 limbs, one each
+  // for the key's bases 2^(64k) delta; at sw = 4 one whole scalar
   void set_extras(int slot, hipStream_t ss) {
     const uint32_t nex = pk->extras[slot];
     if (!nex) return;
     const zk_fr* whole = slot == MSM_A ? r : slot == MSM_B2 ? s : nullptr;
-    if (sound) {   // 1 for alpha_1 / beta_2 / beta_1, then r (delta_1) or s (delta_2) whole
-      ExtrasFr ex{};
-      ex.v[0] = 1;
-      if (whole) for (int k = 0; k < 4; k++) ex.v[4 + k] = whole->l[k];
-      k_set_extras_fr<<<1, 64, 0, ss>>>(scal(slot) + 4 * (size_t)pk->count[slot], ex, 4 * nex);
-      ZK_LAUNCH_CHECK();
-      return;
-    }
     Extras ex{};
     ex.v[0] = 1;
-    if (whole) for (int k = 0; k < 4; k++) ex.v[1 + k] = whole->l[k];
-    k_set_extras<<<1, 64, 0, ss>>>(scal(slot) + pk->count[slot], ex, nex);
+    if (whole) for (int k = 0; k < 4; k++) ex.v[sw + k] = whole->l[k];
+    k_set_extras<<<1, 64, 0, ss>>>(scal(slot) + (size_t)sw * pk->count[slot], ex, sw * nex);
     ZK_LAUNCH_CHECK();
   }
-  // lo64(z) behind compacted positions [lo, hi) of an A / B2 / B1 slot ([0, count): all), and the extras
+  // z behind compacted positions [lo, hi) of an A / B2 / B1 slot ([0, count): all), and the extras
   void gather(int slot, uint32_t lo, uint32_t hi, bool extras, hipStream_t ss) {
     ctx->scal[slot].ensure(sizeof(uint64_t) * sw * std::max<uint32_t>(pk->count[slot] + pk->extras[slot], 1));
-    if (hi > lo && sound) {
-      k_gather_fr<<<ceil_div(hi - lo, 256), 256, 0, ss>>>(reinterpret_cast<const Fr*>(in.d_z),
-                                                         pk->idx[slot].as<uint32_t>() + lo, hi - lo,
-                                                         reinterpret_cast<Fr*>(scal(slot)) + lo);
-      ZK_LAUNCH_CHECK();
-    } else if (hi > lo) {
-      k_gather_lo64<<<ceil_div(hi - lo, 256), 256, 0, ss>>>(in.d_z, 4, pk->idx[slot].as<uint32_t>() + lo, 1u, hi - lo,
-                                                           scal(slot) + lo);
-      ZK_LAUNCH_CHECK();
-    }
+    if (hi > lo)
+      gather_scalars(in.d_z, 4, pk->idx[slot].as<uint32_t>() + lo, 1u, hi - lo, sw, scal(slot) + (size_t)sw * lo, ss);
     if (extras) set_extras(slot, ss);
   }
   void gather_ic(hipStream_t ss) {
-    if (!nic) return;
-    if (sound)
-      k_gather_fr<<<ceil_div(nic, 256), 256, 0, ss>>>(reinterpret_cast<const Fr*>(in.d_z),
-                                                     pk->idx[MSM_IC].as<uint32_t>(), nic,
-                                                     reinterpret_cast<Fr*>(scal(MSM_H)));
-    else
-      k_gather_lo64<<<ceil_div(nic, 256), 256, 0, ss>>>(in.d_z, 4, pk->idx[MSM_IC].as<uint32_t>(), 1u, nic, scal(MSM_H));
-    ZK_LAUNCH_CHECK();
+    gather_scalars(in.d_z, 4, pk->idx[MSM_IC].as<uint32_t>(), 1u, nic, sw, scal(MSM_H), ss);
   }
   void gather_ic_early() {
     gather_ic(s_abi);
@@ -431,33 +409,32 @@ struct ProveRun {
   }
   void gather_ich(hipStream_t ss) {
     if (!ic_ready) gather_ic(ss);
-    const uint32_t cnt = pk->count[MSM_H];
-    if (cnt && !h_direct && sound) {   // never sharded: h_div = 1
-      k_gather_fr<<<ceil_div(cnt, 256), 256, 0, ss>>>(reinterpret_cast<const Fr*>(h_src),
-                                                     pk->idx[MSM_H].as<uint32_t>(), cnt,
-                                                     reinterpret_cast<Fr*>(scal(MSM_H)) + nic);
-      ZK_LAUNCH_CHECK();
-    } else if (cnt && !h_direct) {
-      k_gather_lo64<<<ceil_div(cnt, 256), 256, 0, ss>>>(h_src, 1, pk->idx[MSM_H].as<uint32_t>(), h_div, cnt,
-                                                        scal(MSM_H) + nic);
-      ZK_LAUNCH_CHECK();
-    }
+    // H's scalars sit sw words apart, a shard's H_(shard + h_div d) at d (a sound key: h_div = 1)
+    if (!h_direct)
+      gather_scalars(h_src, sw, pk->idx[MSM_H].as<uint32_t>(), h_div, pk->count[MSM_H], sw,
+                     scal(MSM_H) + (size_t)sw * nic, ss);
   }
-  // One MSM of a sound key over the slot's window copies (MSM_H: [IC | H]; all of
-  // them, or the grouped-window plan over those the key kept), downloaded
+  // the scalars of a whole slot (MSM_H: [IC | H])
+  void gather_slot(int slot, hipStream_t ss) {
+    if (slot == MSM_H) gather_ich(ss);
+    else gather(slot, 0, pk->count[slot], true, ss);
+  }
+  // points (and scalars) of a slot (MSM_H: the [IC | H] vector)
+  uint32_t slot_len(int slot) const { return slot == MSM_H ? pk->ich_tot() : pk->count[slot] + pk->extras[slot]; }
+  // One MSM over a slot's window copies (all of them, or the grouped-window
+  // plan over those the key kept), downloaded
   template <class C>
-  void launch_shared(int slot, const char* tag, hipStream_t gs) {
+  void launch_grouped(int slot, hipStream_t gs) {
     MsmWork& w = ctx->msm[slot];
-    w.tag = serial ? tag : "";
-    const uint32_t n = slot == MSM_H ? pk->ich_tot() : pk->count[slot] + pk->extras[slot];
-    msm_launch_grouped<C>(w, pk->bases[slot].as<typename C::A>(), scal(slot), sw, n, bits, pk->win_c, pk->copies, gs,
-                          pk->stride[slot]);
+    w.tag = serial ? SLOT_TAG[slot] : "";
+    msm_launch_grouped<C>(w, pk->bases[slot].as<typename C::A>(), scal(slot), sw, slot_len(slot), bits, pk->win_c,
+                          pk->copies, gs, pk->stride[slot]);
     msm_download<C>(w, gs);
   }
-  // n points from compacted position lo of a slot's window-shifted bases (MSM_H: the [IC | H] vector)
+  // n points from compacted position lo of a slot's window-shifted bases, one-word scalars (a batch's segment)
   MsmSeg seg(int slot, uint32_t lo, uint32_t n) const {
     MsmSeg sg{pk->bases[slot].p, scal(slot) + lo, n, pk->stride[slot]};
-    sg.wstride = slot == MSM_H ? pk->ich_tot() : pk->count[slot] + pk->extras[slot];
+    sg.wstride = slot_len(slot);
     sg.ioff = lo;
     return sg;
   }
@@ -506,52 +483,53 @@ struct ProveRun {
       launch_part<G1>(k, G1_AB, 2, ctx->part_abi, "msm_g1_a_b1_part", "AB/", "ABp/", s_abi);
     }
   }
-  // a G1 batch over whole slots
-  void launch_batch(const int* slots, int k, const char* tag, hipStream_t gs) {
-    Range range(k == 1 ? "msm_g1_ic_h" : "msm_g1_a_b1");
-    MsmSeg segs[MSM_MAXSEG];
-    for (int i = 0; i < k; i++) {
-      const int sl = slots[i];
-      if (sl == MSM_H) gather_ich(gs);
-      else gather(sl, 0, pk->count[sl], true, gs);
-      segs[i] = seg(sl, 0, sl == MSM_H ? pk->ich_tot() : pk->count[sl] + pk->extras[sl]);
+  // A G1 group over whole slots (A + B1, or IC+H alone), its gathers included;
+  // ev_done[slots[0]] stands for the group.  One-word scalars run the group
+  // as ONE batch (msm_launch_batch: one sort, merge and bucket reduction);
+  // whole scalars run one grouped-window MSM per slot, in order:
+  // msm_front_impl batches one-word scalars only, and A and B1 as one batch at
+  // sw = 4 measured slower in the overlapped prove (DESIGN.md 2.8,
+  // profiles/sound_ab_batch_rejected.txt).  finish_g1 reads the result back
+  // by the same rule; nothing else in a proof depends on it.
+  bool g1_batched() const { return sw == 1; }
+  void launch_g1(const int* slots, int k, const char* range_name, const char* tag, hipStream_t gs) {
+    Range range(range_name);
+    if (g1_batched()) {
+      MsmSeg segs[MSM_MAXSEG];
+      for (int i = 0; i < k; i++) {
+        gather_slot(slots[i], gs);
+        segs[i] = seg(slots[i], 0, slot_len(slots[i]));
+      }
+      MsmWork& w = ctx->msm[slots[0]];
+      w.tag = serial ? tag : "";
+      msm_launch_batch<G1>(w, segs, k, 64, pk->win_c, gs);
+      msm_download<G1>(w, gs);
+    } else {
+      for (int i = 0; i < k; i++) {
+        gather_slot(slots[i], gs);
+        launch_grouped<G1>(slots[i], gs);
+      }
     }
-    MsmWork& w = ctx->msm[slots[0]];
-    w.tag = serial ? tag : "";
-    msm_launch_batch<G1>(w, segs, k, 64, pk->win_c, gs);
-    msm_download<G1>(w, gs);
     ZK_HIP(hipEventRecord(ctx->ev_done[slots[0]], gs));
+  }
+  // the sum of slot slots[i] of a finished group
+  host::X<host::Fq> finish_g1(const int* slots, int i) const {
+    return g1_batched() ? msm_finish_seg<G1>(ctx->msm[slots[0]], i) : msm_finish<G1>(ctx->msm[slots[i]]);
   }
   // a device witness: G2 (pi_B), then A + B1 + IC, both starting with it
   void launch_whole() {
     if (!serial) ZK_HIP(hipStreamWaitEvent(s_g2, ctx->ev_scal, 0));
     {
       Range range("msm_g2");
-      MsmWork& w = ctx->msm[MSM_B2];
-      w.tag = serial ? "B2/" : "";
-      gather(MSM_B2, 0, pk->count[MSM_B2], true, s_g2);
-      msm_launch_grouped<G2>(w, pk->bases[MSM_B2].as<G2A>(), scal(MSM_B2), sw, pk->count[MSM_B2] + pk->extras[MSM_B2],
-                             bits, pk->win_c, pk->copies, s_g2, pk->stride[MSM_B2]);
-      msm_download<G2>(w, s_g2);
+      gather_slot(MSM_B2, s_g2);
+      launch_grouped<G2>(MSM_B2, s_g2);
       ZK_HIP(hipEventRecord(ctx->ev_done[MSM_B2], s_g2));
     }
     if (!serial) {
       ZK_HIP(hipStreamWaitEvent(s_abi, ctx->ev_scal, 0));
       gather_ic_early();
     }
-    if (!sound) {
-      launch_batch(G1_AB, 2, "AB/", s_abi);
-      return;
-    }
-    // whole scalars: A, then B1, each its own MSM (msm_front_impl batches
-    // one-word scalars only: the two as one batch at sw = 4 measured slower in
-    // the overlapped prove); ev_done[MSM_A] still stands for both
-    Range range("msm_g1_a_b1");
-    gather(MSM_A, 0, pk->count[MSM_A], true, s_abi);
-    launch_shared<G1>(MSM_A, "A/", s_abi);
-    gather(MSM_B1, 0, pk->count[MSM_B1], true, s_abi);
-    launch_shared<G1>(MSM_B1, "B1/", s_abi);
-    ZK_HIP(hipEventRecord(ctx->ev_done[MSM_A], s_abi));
+    launch_g1(G1_AB, 2, "msm_g1_a_b1", "AB/", s_abi);
   }
 
   // ---- the quotient, then IC + H on the main stream
@@ -562,10 +540,10 @@ struct ProveRun {
       ctx->tmp_scal.ensure(sizeof(uint64_t) * (pk->n / pk->nshards));
       dist_quotient(ctx, pk, in.d_z, *ctx->exch, ctx->dq, flags(), ctx->tmp_scal.as<uint64_t>(), st);
     } else {
-      // (Az, Bz, Cz) -> lo64(H): in place in the IC+H scalars, else in
+      // (Az, Bz, Cz) -> H's scalars: in place in the IC+H scalars, else in
       // tmp_scal (sized here, before its pointer is taken)
       ctx->tmp_scal.ensure(sizeof(uint64_t) * sw * pk->n);
-      quotient(ctx, pk, in.d_z, st, h_direct ? scal(MSM_H) + (size_t)sw * nic : ctx->tmp_scal.as<uint64_t>());
+      quotient(ctx, pk, in.d_z, sw, st, h_direct ? scal(MSM_H) + (size_t)sw * nic : ctx->tmp_scal.as<uint64_t>());
     }
     h_src = ctx->tmp_scal.as<uint64_t>();
   }
@@ -602,14 +580,7 @@ struct ProveRun {
     flags_agreed = dist && ctx->exch->agree_max_dev(flags(), st);
     ZK_HIP(hipMemcpyAsync(ctx->flags_host.p, ctx->flags.p, 4, hipMemcpyDeviceToHost, st));
     if (ic_ready) ZK_HIP(hipStreamWaitEvent(st, ctx->ev_ic, 0));
-    if (sound) {
-      Range range("msm_g1_ic_h");
-      gather_ich(st);
-      launch_shared<G1>(MSM_H, "ICH/", st);
-      ZK_HIP(hipEventRecord(ctx->ev_done[MSM_H], st));
-    } else {
-      launch_batch(G1_ICH, 1, "ICH/", st);
-    }
+    launch_g1(G1_ICH, 1, "msm_g1_ic_h", "ICH/", st);
     if (ph_span >= 0) {
       for (int sl : WAITS) ZK_HIP(hipStreamWaitEvent(st, ctx->ev_done[sl], 0));
       ctx->prof.end(st, ph_span);
@@ -641,11 +612,11 @@ struct ProveRun {
           p.B2 = msm_finish<G2>(ctx->msm[slot]);
           if (in.early) host_to_abi<G2>(p.B2, reinterpret_cast<uint64_t*>(&in.early->b));
         } else if (slot == MSM_A) {
-          p.A = sound ? msm_finish<G1>(ctx->msm[MSM_A]) : msm_finish_seg<G1>(ctx->msm[slot], 0);
-          p.B1 = sound ? msm_finish<G1>(ctx->msm[MSM_B1]) : msm_finish_seg<G1>(ctx->msm[slot], 1);
+          p.A = finish_g1(G1_AB, 0);
+          p.B1 = finish_g1(G1_AB, 1);
           ab_done = true;
         } else {
-          p.IC = sound ? msm_finish<G1>(ctx->msm[slot]) : msm_finish_seg<G1>(ctx->msm[slot], 0);   // IC + H_1
+          p.IC = finish_g1(G1_ICH, 0);   // IC + H_1
           p.H = host::inf<host::Fq>();
         }
         done[wi] = progressed = true;
@@ -721,9 +692,12 @@ int prove_impl(zk_ctx* ctx, const zk_pk_dev* pk, const void* d_z, size_t zlen, s
   ProveInput in{reinterpret_cast<const uint64_t*>(d_z)};
   in.early = &ab;
   in.z_host = z_host;
+  // How a host witness reaches the device is decided here, once.  A reference
+  // key takes the split path (ProveRun::launch_split: z goes up in parts under
+  // the MSMs of the parts already there, which are batches of one-word
+  // scalars).  A sound key's goes up whole first and then takes the device
+  // path, like a device witness.
   if (pk->sound() && z_host) {
-    // a sound key's host witness goes up whole, then takes the device path
-    // (the split, overlapped upload is the 64-bit schedule's)
     ZK_HIP(hipMemcpyAsync(const_cast<void*>(d_z), z_host, sizeof(zk_fr) * zlen, hipMemcpyHostToDevice, ctx->stream));
     in.z_host = nullptr;
   }

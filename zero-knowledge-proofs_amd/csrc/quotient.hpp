@@ -1,5 +1,6 @@
 // quotient.hpp -- pieces of the QAP quotient shared by the single-GPU path
-// (prove.hip) and the distributed one (dist.hip).
+// (prove.hip) and the distributed one (dist.hip), and the scalar store that
+// these and setup.hip share.
 #pragma once
 #include "ctx.hpp"
 
@@ -25,6 +26,18 @@ __device__ __forceinline__ Fr row_dot(const uint64_t* __restrict__ rp, const uin
     acc = fp_add(acc, zv);
   }
   return acc;
+}
+
+// Scalar i of an MSM's scalar vector, SW u64 words each, from a Montgomery
+// Fr: the low 64 bits of its canonical value (SW = 1, the reference's
+// truncation, core:156-161 / 203-208) or the whole canonical value (SW = 4,
+// a sound key).  The one place where the two key modes differ per element.
+template <int SW>
+__device__ __forceinline__ void st_scal(uint64_t* __restrict__ out, size_t i, const Fr& mont) {
+  static_assert(SW == 1 || SW == 4, "a scalar is its lo64 or whole");
+  const Fr c = fp_from_mont(mont);
+  if constexpr (SW == 1) out[i] = (uint64_t)c.v[0] | ((uint64_t)c.v[1] << 32);
+  else st_vec(reinterpret_cast<Fr*>(out) + i, c);
 }
 
 // Device-side view of a pk's CSR.

@@ -131,16 +131,14 @@ __global__ void __launch_bounds__(256) k_colsum(const uint64_t* __restrict__ cp,
   st_vec(&out[i], acc);
 }
 
-__device__ __forceinline__ uint64_t lo64_of(const Fr& m) {
-  Fr c = fp_from_mont(m);
-  return (uint64_t)c.v[0] | ((uint64_t)c.v[1] << 32);
-}
-
 struct SetupConsts {
-  Fr al, be, dinv, ginv;  // Montgomery: a~, b~, d~^-1, g~^-1
+  Fr al, be, dinv, ginv;  // Montgomery: a~, b~, d~^-1, g~^-1 (sound: the full-width alpha, beta, delta^-1, gamma^-1)
   uint64_t V, num_public;
 };
-// per variable i: lo64 scalars for a_g1, b_g1 (= b_g2), pk ic (i > l) / vk ic (i <= l)
+// per variable i: the scalars for a_g1, b_g1 (= b_g2), pk ic (i > l) / vk ic
+// (i <= l), SW words each (st_scal: 1 = lo64, the reference; 4 = whole, a
+// sound setup, where nothing is truncated)
+template <int SW>
 __global__ void __launch_bounds__(256) k_setup_scalars(const Fr* __restrict__ av, const Fr* __restrict__ bv,
                                                        const Fr* __restrict__ cv, SetupConsts k,
                                                        uint64_t* __restrict__ sa, uint64_t* __restrict__ sb,
@@ -148,30 +146,17 @@ __global__ void __launch_bounds__(256) k_setup_scalars(const Fr* __restrict__ av
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= k.V) return;
   const Fr a = ld_vec(&av[i]), b = ld_vec(&bv[i]), c = ld_vec(&cv[i]);
-  sa[i] = lo64_of(a);
-  sb[i] = lo64_of(b);
+  st_scal<SW>(sa, i, a);
+  st_scal<SW>(sb, i, b);
   const Fr t = fp_add(fp_add(fp_mul(k.be, a), fp_mul(k.al, b)), c);
-  if (i > k.num_public) sic[i - k.num_public - 1] = lo64_of(fp_mul(t, k.dinv));
-  else svk[i] = lo64_of(fp_mul(t, k.ginv));
+  if (i > k.num_public) st_scal<SW>(sic, i - k.num_public - 1, fp_mul(t, k.dinv));
+  else st_scal<SW>(svk, i, fp_mul(t, k.ginv));
 }
-__global__ void __launch_bounds__(256) k_lo64(const Fr* __restrict__ in, size_t n, uint64_t* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = lo64_of(ld_vec(&in[i]));
-}
-// Sound setup: the same scalars whole, as canonical 4-limb Fr (k holds the
-// full-width alpha, beta, delta^-1, gamma^-1); nothing is truncated.
-__global__ void __launch_bounds__(256) k_setup_scalars_full(const Fr* __restrict__ av, const Fr* __restrict__ bv,
-                                                            const Fr* __restrict__ cv, SetupConsts k,
-                                                            Fr* __restrict__ sa, Fr* __restrict__ sb,
-                                                            Fr* __restrict__ sic, Fr* __restrict__ svk) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k.V) return;
-  const Fr a = ld_vec(&av[i]), b = ld_vec(&bv[i]), c = ld_vec(&cv[i]);
-  st_vec(&sa[i], fp_from_mont(a));
-  st_vec(&sb[i], fp_from_mont(b));
-  const Fr t = fp_add(fp_add(fp_mul(k.be, a), fp_mul(k.al, b)), c);
-  if (i > k.num_public) st_vec(&sic[i - k.num_public - 1], fp_from_mont(fp_mul(t, k.dinv)));
-  else st_vec(&svk[i], fp_from_mont(fp_mul(t, k.ginv)));
+static void setup_scalars(const Fr* av, const Fr* bv, const Fr* cv, const SetupConsts& k, int sw, uint64_t* sa,
+                          uint64_t* sb, uint64_t* sic, uint64_t* svk, hipStream_t st) {
+  if (sw == 1) k_setup_scalars<1><<<ceil_div(k.V, 256), 256, 0, st>>>(av, bv, cv, k, sa, sb, sic, svk);
+  else k_setup_scalars<4><<<ceil_div(k.V, 256), 256, 0, st>>>(av, bv, cv, k, sa, sb, sic, svk);
+  ZK_LAUNCH_CHECK();
 }
 
 // XYZZ = sum_w T[w][byte_w(k)]  (<= 8 mixed additions), k = scal[idx ? idx[i] : i]
@@ -501,21 +486,10 @@ int setup_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_setup_params* P, uint
   K.ginv = fr_dev(ginv);
   K.V = V;
   K.num_public = num_public;
-  if (sound)
-    k_setup_scalars_full<<<ceil_div(V, 256), 256, 0, st>>>(abc[0].as<Fr>(), abc[1].as<Fr>(), abc[2].as<Fr>(), K,
-                                                           sa.as<Fr>(), sb.as<Fr>(), sic.as<Fr>(), svk.as<Fr>());
-  else
-    k_setup_scalars<<<ceil_div(V, 256), 256, 0, st>>>(abc[0].as<Fr>(), abc[1].as<Fr>(), abc[2].as<Fr>(), K,
-                                                      sa.as<uint64_t>(), sb.as<uint64_t>(), sic.as<uint64_t>(),
-                                                      svk.as<uint64_t>());
-  ZK_LAUNCH_CHECK();
+  setup_scalars(abc[0].as<Fr>(), abc[1].as<Fr>(), abc[2].as<Fr>(), K, sw, sa.as<uint64_t>(), sb.as<uint64_t>(),
+                sic.as<uint64_t>(), svk.as<uint64_t>(), st);
   fr_powers(tp.as<Fr>(), fr_dev(t), fr_dev(hk), n, st);   // t~^i / d~ (sound: tau^i Z(tau) / delta)
-  if (sound) {
-    fr_from_mont(tp.as<Fr>(), sh.as<uint64_t>(), n, st);
-  } else {
-    k_lo64<<<ceil_div(n, 256), 256, 0, st>>>(tp.as<Fr>(), n, sh.as<uint64_t>());
-    ZK_LAUNCH_CHECK();
-  }
+  fr_to_scalars(tp.as<Fr>(), n, sw, sh.as<uint64_t>(), st);
 
   // ---- full-width generator multiples (host; setup:166-171) ----
   const auto G1h = g1_gen_host();

@@ -554,6 +554,42 @@ int zk_groth16_verify_many(zk_ctx *ctx, const zk_vk *vk, const zk_proof *proofs,
 int zk_groth16_verify_many_sound(zk_ctx *ctx, const zk_vk *vk, const zk_proof *proofs,
                                  const zk_fr *public_inputs, size_t n_inputs, size_t n_proofs,
                                  uint8_t *status);
+/* n proofs of 192 bytes each (a | b | c, the encoding of
+ * zk_proof_serialize_compressed) -> n zk_proof, decoded on the GPU: ark
+ * CanonicalDeserialize (compressed, Validate::Yes) on n Proof, what
+ * zk_proof_deserialize_compressed does for one on the host.  point_status:
+ * 3 n bytes of zk_point_status, entry 3k + j for point a, b, c of proof k (may
+ * be NULL).  All three points of every proof are decoded and get their own
+ * status (no early exit inside a proof); an invalid point's words are zero.
+ * ZK_OK when every point is valid, ZK_ERR_ARG when any is not (out and
+ * point_status still filled, zk_last_error names the first: proof index, which
+ * point, status text), ZK_ERR_DEVICE on a HIP error, n == 0 -> ZK_OK.  The
+ * subgroup test is Scott's endomorphism criterion (phi(P) = -[x^2]P on G1,
+ * psi(P) = [x]P on G2), equivalent to [r]P == O for points on the curve.  The
+ * batch crosses the GPU in chunks of ZK_OPT_VERIFY_CHUNK proofs. */
+int zk_proofs_deserialize_compressed(zk_ctx *ctx, const uint8_t *in, size_t n, zk_proof *out,
+                                     uint8_t *point_status);
+/* zk_groth16_verify_many from wire bytes: proofs is n_proofs x 192 bytes, and
+ * decode, curve check, subgroup check and pairing check all run on the GPU in
+ * one call (the decoded proofs never visit the host).  It replaces ark
+ * CanonicalDeserialize (compressed, Validate::Yes) on Proof followed by
+ * Verifier::verify.  status[k]: ZK_VERIFY_MALFORMED where
+ * zk_proof_deserialize_compressed refuses proof k's 192 bytes (encoding,
+ * range, curve, SUBGROUP), else what zk_groth16_verify gives for the decoded
+ * proof.  point_status as in zk_proofs_deserialize_compressed (may be NULL).
+ * Return codes, vk validation and chunking exactly as zk_groth16_verify_many
+ * (ZK_OK whatever the statuses are).  Because the decoder checks the subgroup,
+ * the "unspecified status" clause of zk_groth16_verify_many does not apply
+ * here: every status is fully specified. */
+int zk_groth16_verify_many_bytes(zk_ctx *ctx, const zk_vk *vk, const uint8_t *proofs,
+                                 const zk_fr *public_inputs, size_t n_inputs, size_t n_proofs,
+                                 uint8_t *status, uint8_t *point_status);
+/* The same for a sound key, as zk_groth16_verify_many_sound: else what
+ * zk_groth16_verify_sound gives, a public input >= r making that proof
+ * MALFORMED (its point statuses can then all be ZK_POINT_OK). */
+int zk_groth16_verify_many_bytes_sound(zk_ctx *ctx, const zk_vk *vk, const uint8_t *proofs,
+                                       const zk_fr *public_inputs, size_t n_inputs, size_t n_proofs,
+                                       uint8_t *status, uint8_t *point_status);
 /* n_products pairing products on the GPU, one lane per product: product j =
  * prod_{i<k} e(g1[jk+i], g2[jk+i]) with k = pairs_per_product; status[j] as
  * above (ACCEPT: the product is 1 -- zk_pairing_product_is_one's *result = 1;

@@ -16,6 +16,21 @@ plain square-and-multiply final exponentiation), not an optimized CPU
 library.
 
   python tools/verify_bench.py [--out profiles/verify_bench.json]
+
+--bytes: the same sizes from the proofs' 192 wire bytes, three pipelines in
+one process, written to profiles/verify_bytes_bench.json:
+  (a) Context.verify_many_bytes (zk_groth16_verify_many_bytes): decode,
+      subgroup test and verification on the GPU in one call;
+  (b) the calls that existed before it: restride the records on the host,
+      zk_g1_decompress over A and C, zk_g2_decompress over B, reassemble the
+      zk_proof words, verify_many;
+  (c) the host decoder (zk_proof_deserialize_compressed, one thread, measured
+      here over --host-proofs proofs) spread over --cpus CPUs, plus verify_many.
+Kernel times come from one extra run of (a) and of (b) under zk_ctx_profile:
+proof_decode_g1 / proof_decode_g2 (the endomorphism subgroup test) against
+points_g1 / points_g2 ([r]P == O) on the same points, per point.
+
+  python tools/verify_bench.py --bytes
 """
 import argparse
 import importlib
@@ -45,6 +60,83 @@ def timed(fn, warmup, runs):
     return {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts), "runs": runs}
 
 
+def timed_alternating(fns, warmup, runs):
+    """timed() for several pipelines measured against each other: one call of each in turn per
+    round, so that a drift of the machine falls on all of them alike"""
+    ts = {k: [] for k in fns}
+    for i in range(warmup + runs):
+        for k, fn in fns.items():
+            t0 = time.perf_counter()
+            fn()
+            if i >= warmup:
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+    return {k: {"median_ms": statistics.median(t), "min_ms": min(t), "max_ms": max(t), "runs": runs}
+            for k, t in ts.items()}
+
+
+def bytes_leg(zkp, ctx, vk, words, inputs, args, res):
+    """the three pipelines from wire bytes at every size (module docstring)"""
+    recs = np.array([np.frombuffer(zkp.Proof(w).serialize_compressed(), dtype=np.uint8) for w in words])
+    k = args.host_proofs
+    host_recs = [recs[i % len(recs)].tobytes() for i in range(k)]
+    r = timed(lambda: [zkp.Proof.deserialize_compressed(b) for b in host_recs], 1, 5)
+    r["proofs"] = k
+    r["ms_per_proof"] = r["median_ms"] / k
+    r["bar_ms_per_proof"] = r["ms_per_proof"] / args.cpus
+    res["host_decode"] = r
+    print("host_decode", json.dumps(r), flush=True)
+    host_decode_bar = r["bar_ms_per_proof"]
+
+    def existing_calls(data, inp):
+        a = data.reshape(-1, 192)
+        n = len(a)
+        g1 = np.ascontiguousarray(np.stack([a[:, :48], a[:, 144:]], axis=1))       # A and C of a proof side by side
+        w1, s1 = ctx.g1_decompress(g1)
+        w2, s2 = ctx.g2_decompress(np.ascontiguousarray(a[:, 48:144]))
+        assert not s1.any() and not s2.any()
+        w1 = w1.reshape(n, 2, 13)
+        pw = np.concatenate([w1[:, 0], w2, w1[:, 1]], axis=1)
+        return ctx.verify_many(vk, pw, inp), pw
+
+    def profiled(fn):
+        ctx.profile(1)
+        fn()
+        prof = ctx.profile_read()
+        ctx.profile(0)
+        return {ph: v["ms"] for ph, v in prof.items()}
+
+    for n in args.sizes:
+        reps = -(-n // len(words))
+        want = np.ascontiguousarray(np.tile(words, (reps, 1))[:n])
+        data = np.ascontiguousarray(np.tile(recs, (reps, 1))[:n])
+        inp = np.ascontiguousarray(np.tile(inputs, (reps, 1, 1))[:n])
+        st, pst = ctx.verify_many_bytes(vk, data, inp, point_status=True)
+        assert (st == zkp.ZK_VERIFY_ACCEPT).all() and not pst.any()
+        dw, _ = ctx.proofs_deserialize(data)
+        assert np.array_equal(dw, want)
+        st, pw = existing_calls(data, inp)
+        assert (st == zkp.ZK_VERIFY_ACCEPT).all() and np.array_equal(pw, want)
+        t = timed_alternating({"a": lambda: ctx.verify_many_bytes(vk, data, inp),
+                               "b": lambda: existing_calls(data, inp),
+                               "v": lambda: ctx.verify_many(vk, want, inp)}, args.warmup, args.runs)
+        a, b, v = t["a"], t["b"], t["v"]
+        ka = profiled(lambda: ctx.verify_many_bytes(vk, data, inp))
+        kb = profiled(lambda: existing_calls(data, inp))
+        c_ms = n * host_decode_bar + v["median_ms"]
+        dec_a = ka.get("proof_decode_g1", 0.0) + ka.get("proof_decode_g2", 0.0)
+        r = {"proofs": n, "a_verify_many_bytes": a, "b_existing_calls": b, "verify_many_words": v,
+             "c_host_decode_bar_plus_verify_ms": c_ms, "a_kernel_ms": ka, "b_kernel_ms": kb,
+             "a_ms_per_proof": a["median_ms"] / n, "b_over_a": b["median_ms"] / a["median_ms"],
+             "c_over_a": c_ms / a["median_ms"], "a_below_b": a["median_ms"] < b["median_ms"],
+             "decode_share_of_a_kernels": dec_a / (dec_a + ka.get("verify", 0.0)),
+             "g1_ns_per_point": {"endomorphism": 1e6 * ka.get("proof_decode_g1", 0.0) / (2 * n),
+                                 "r_times_p": 1e6 * kb.get("points_g1", 0.0) / (2 * n)},
+             "g2_ns_per_point": {"endomorphism": 1e6 * ka.get("proof_decode_g2", 0.0) / n,
+                                 "r_times_p": 1e6 * kb.get("points_g2", 0.0) / n}}
+        res["bytes_%d" % n] = r
+        print("bytes_%d" % n, json.dumps(r), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[1, 64, 4096, 65536])
@@ -52,8 +144,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--cpus", type=int, default=16)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "verify_bench.json"))
+    ap.add_argument("--bytes", action="store_true", help="the wire-bytes pipelines (module docstring)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "verify_bytes_bench.json" if args.bytes else "verify_bench.json")
     if args.runs < 5:
         ap.error("--runs must be at least 5")
 
@@ -96,7 +191,9 @@ def main():
     print("host_verify", json.dumps(r), flush=True)
 
     with zkp.Context(0) as ctx:
-        for n in args.sizes:
+        if args.bytes:
+            bytes_leg(zkp, ctx, vk, words, inputs, args, res)
+        for n in [] if args.bytes else args.sizes:
             reps = -(-n // len(words))
             w = np.ascontiguousarray(np.tile(words, (reps, 1))[:n])
             inp = np.ascontiguousarray(np.tile(inputs, (reps, 1, 1))[:n])

@@ -59,6 +59,7 @@ EXPORTS = (
     "zk_groth16_setup_sound", "zk_groth16_setup_sound_dev", "zk_pk_upload_sound", "zk_pk_is_sound",
     "zk_groth16_verify_sound", "zk_groth16_verify_many_sound",
     "zk_msm_g1_upload_copies", "zk_msm_g2_upload_copies", "zk_pk_device_bytes",
+    "zk_proofs_deserialize_compressed", "zk_groth16_verify_many_bytes", "zk_groth16_verify_many_bytes_sound",
 )
 # include/zkp_test.h (libzkp_amd_test.so)
 TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fault_after_exchange",
@@ -82,6 +83,7 @@ ZK_POINT_OK, ZK_POINT_ENCODING, ZK_POINT_NOT_CANONICAL, ZK_POINT_NOT_ON_CURVE, Z
 POINT_STATUS_TEXT = ("valid", "bad encoding flags", "coordinate not below p", "not on the curve",
                      "not in the prime-order subgroup")
 G1_BYTES, G2_BYTES = 48, 96
+PROOF_BYTES, PROOF_WORDS = 192, 51
 CSRC = os.path.join(_HERE, "csrc")
 
 
@@ -543,6 +545,22 @@ class Context:
         return self._validate("zk_g2_validate", arr, G2_WORDS)
 
     # ---- batch verification on the GPU (one lane per proof / product) ----
+    @staticmethod
+    def _verify_inputs(vk, inputs, n):
+        """the public inputs of n proofs as an (n, n_inputs, 4) uint64 array"""
+        if isinstance(inputs, np.ndarray) and inputs.ndim == 3:
+            inp = np.ascontiguousarray(inputs, dtype=np.uint64)
+        else:
+            rows = [_fr_rows(r) for r in inputs]
+            if len({len(r) for r in rows}) > 1:
+                raise InvalidWitness("verify_many: rows of public inputs of different lengths")
+            inp = np.zeros((len(rows), len(rows[0]) if rows else vk.num_public, 4), dtype=np.uint64)
+            for k, r in enumerate(rows):
+                inp[k] = r
+        if len(inp) != n or inp.shape[2] != 4:
+            raise ValueError("verify_many: one row of public inputs (n_inputs x 4 words) per proof")
+        return inp
+
     def verify_many(self, vk, proofs, inputs, sound=False):
         """zk_groth16_verify_many: n proofs (Proof objects, or an (n, 51)
         uint64 array of their words) against one vk, inputs an (n, n_inputs,
@@ -556,23 +574,56 @@ class Context:
         else:
             pw = np.ascontiguousarray([p.words for p in proofs], dtype=np.uint64).reshape(-1, 2 * G1_WORDS + G2_WORDS)
         n = len(pw)
-        if isinstance(inputs, np.ndarray) and inputs.ndim == 3:
-            inp = np.ascontiguousarray(inputs, dtype=np.uint64)
-        else:
-            rows = [_fr_rows(r) for r in inputs]
-            if len({len(r) for r in rows}) > 1:
-                raise InvalidWitness("verify_many: rows of public inputs of different lengths")
-            inp = np.zeros((len(rows), len(rows[0]) if rows else vk.num_public, 4), dtype=np.uint64)
-            for k, r in enumerate(rows):
-                inp[k] = r
-        if len(inp) != n or inp.shape[2] != 4:
-            raise ValueError("verify_many: one row of public inputs (n_inputs x 4 words) per proof")
+        inp = self._verify_inputs(vk, inputs, n)
         st = np.zeros(n, dtype=np.uint8)
         fn = lib().zk_groth16_verify_many_sound if sound else lib().zk_groth16_verify_many
         rc = fn(C.c_void_p(self._h), C.byref(vk.s), _p(pw) if n else None, _p(inp) if inp.size else None,
                 C.c_size_t(inp.shape[1]), C.c_size_t(n), _p(st) if n else None)
         _check(rc, self, "zk_groth16_verify_many")
         return st
+
+    @staticmethod
+    def _proof_bytes(data, what):
+        """bytes, or an (n, 192) uint8 array -> (flat uint8 array, n)"""
+        if isinstance(data, np.ndarray):
+            buf = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        else:
+            buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        if len(buf) % PROOF_BYTES:
+            raise ValueError(f"{what}: {len(buf)} bytes is not a whole number of {PROOF_BYTES}-byte proofs")
+        return buf, len(buf) // PROOF_BYTES
+
+    def proofs_deserialize(self, data):
+        """zk_proofs_deserialize_compressed: n compressed proofs (bytes, or an
+        (n, 192) uint8 array) -> ((n, 51) uint64 proof words, (n, 3) uint8
+        zk_point_status of a, b, c).  An invalid point has a non-zero status
+        and zero words; nothing is raised for it."""
+        buf, n = self._proof_bytes(data, "proofs_deserialize")
+        out = np.zeros((n, PROOF_WORDS), dtype=np.uint64)
+        pst = np.zeros((n, 3), dtype=np.uint8)
+        if n:
+            rc = lib().zk_proofs_deserialize_compressed(C.c_void_p(self._h), _p(buf), C.c_size_t(n), _p(out), _p(pst))
+            if not (rc == ZK_ERR_ARG and pst.any()):   # invalid points are reported by their status
+                _check(rc, self, "zk_proofs_deserialize_compressed")
+        return out, pst
+
+    def verify_many_bytes(self, vk, data, inputs, sound=False, point_status=False):
+        """zk_groth16_verify_many_bytes: verify_many on n compressed proofs
+        (bytes, or an (n, 192) uint8 array), decoded and subgroup-checked on
+        the GPU in the same call -> n uint8 ZK_VERIFY_* statuses, MALFORMED
+        where Proof.deserialize_compressed raises, else what Verifier.verify
+        says.  point_status: also return the (n, 3) zk_point_status of a, b,
+        c.  sound: zk_groth16_verify_many_bytes_sound."""
+        buf, n = self._proof_bytes(data, "verify_many_bytes")
+        inp = self._verify_inputs(vk, inputs, n)
+        st = np.zeros(n, dtype=np.uint8)
+        pst = np.zeros((n, 3), dtype=np.uint8)
+        fn = lib().zk_groth16_verify_many_bytes_sound if sound else lib().zk_groth16_verify_many_bytes
+        rc = fn(C.c_void_p(self._h), C.byref(vk.s), _p(buf) if n else None, _p(inp) if inp.size else None,
+                C.c_size_t(inp.shape[1]), C.c_size_t(n), _p(st) if n else None,
+                _p(pst) if n and point_status else None)
+        _check(rc, self, "zk_groth16_verify_many_bytes")
+        return (st, pst) if point_status else st
 
     def test_fixed_base(self, scalars, g2=False):
         """zk_test_fixed_base_g1 / _g2 (test library): scalars (ints, or (n, 4)
@@ -1436,6 +1487,36 @@ class Verifier:
         if len(bad):
             raise ValueError(f"verify_many: proof {int(bad[0])} has a point that is not canonical or not on its curve"
                              + (", or a public input that is not below r" if sound else ""))
+        return st == ZK_VERIFY_ACCEPT
+
+    @staticmethod
+    def verify_many_bytes(vk, proofs_and_inputs, ctx=None):
+        """verify_many on compressed proofs: proofs_and_inputs is n pairs
+        (192 bytes, public inputs); decode, subgroup check and pairing check
+        run on the GPU (Context.verify_many_bytes) -> bool array, entry k what
+        verify(vk, Proof.deserialize_compressed(bytes_k), inputs_k) returns.
+        ValueError naming the first malformed proof, its failing point and
+        why; InvalidWitness on an input-count mismatch."""
+        ctx = ctx or default_context()
+        rows = [_fr_rows(inp) for _, inp in proofs_and_inputs]
+        if any(len(r) != vk.num_public for r in rows):
+            raise InvalidWitness("verify_many_bytes: a proof's public inputs do not match vk.num_public")
+        if any(len(b) != PROOF_BYTES for b, _ in proofs_and_inputs):
+            raise ValueError(f"verify_many_bytes: a compressed Proof is {PROOF_BYTES} bytes")
+        inp = np.zeros((len(rows), vk.num_public, 4), dtype=np.uint64)
+        for k, r in enumerate(rows):
+            inp[k] = r
+        sound = getattr(vk, "sound", False)
+        st, pst = ctx.verify_many_bytes(vk, b"".join(bytes(b) for b, _ in proofs_and_inputs), inp, sound=sound,
+                                        point_status=True)
+        bad = np.flatnonzero(st == ZK_VERIFY_MALFORMED)
+        if len(bad):
+            k = int(bad[0])
+            pts = np.flatnonzero(pst[k])
+            if len(pts):
+                j = int(pts[0])
+                raise ValueError(f"verify_many_bytes: proof {k} point {'abc'[j]}: {POINT_STATUS_TEXT[pst[k][j]]}")
+            raise ValueError(f"verify_many_bytes: proof {k} has a public input that is not below r")
         return st == ZK_VERIFY_ACCEPT
 
 

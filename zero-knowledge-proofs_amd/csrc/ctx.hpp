@@ -73,6 +73,12 @@ struct zk_ctx {
   zk::NttDomain& domain(uint32_t log_n);
 };
 
+namespace zk {
+// The proof decoder's device stage (points.hip), shared with the verification
+// that runs behind it (pairing.hip).
+void proofs_decode_launch(zk_ctx* ctx, hipStream_t st, const uint8_t* d_in, size_t m, uint64_t* d_out, uint8_t* d_pst);
+}  // namespace zk
+
 struct zk_pk_dev {
   int device = 0;
   uint64_t V = 0, n = 0, nc = 0, num_public = 0;

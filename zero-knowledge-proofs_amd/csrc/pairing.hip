@@ -4,6 +4,9 @@
 // each (zk_pairing_products).  What verify.hip's zk_groth16_verify and
 // zk_pairing_product_is_one do for one proof or product on a host core, these
 // kernels do for a batch; the host code stays the reference.
+// zk_groth16_verify_many_bytes puts points.hip's proof decoder in front of
+// the same kernel: ark CanonicalDeserialize (compressed, Validate::Yes) on
+// Proof, then Verifier::verify, from the proofs' 192 wire bytes.
 //
 // Per call the host prepares what every lane shares (pairing_tables): the
 // Miller value of (-alpha, beta), and for gamma and delta the PR_STEPS affine
@@ -230,8 +233,16 @@ static bool pairing_tables(const zk_vk& vk, size_t n_inputs, std::vector<uint32_
 // ---- drivers -------------------------------------------------------------------------
 // As points_run: the batch crosses the GPU in chunks of ctx->verify_chunk
 // proofs (products) on the ctx's main stream; buffers belong to the call.
-static int verify_many_run(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs, const zk_fr* inputs, size_t n_inputs,
-                           size_t n, uint8_t* status, bool sound) {
+// bytes (zk_groth16_verify_many_bytes): the chunk goes up as 192-byte
+// compressed proofs and the proof decoder (points.hip) writes the zk_proof
+// records into the buffer the verify kernel reads -- decoded proofs never
+// visit the host.  An invalid point's words are all zero, infinity word
+// included, and (0, 0) is on neither curve: pr_load_g1 / pr_load_g2 refuse it,
+// which makes the proof MALFORMED with the verify kernel unchanged (it does
+// not read the point statuses).
+static int verify_many_run(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs, const uint8_t* bytes,
+                           const zk_fr* inputs, size_t n_inputs, size_t n, uint8_t* status, uint8_t* point_status,
+                           bool sound) {
   if (n_inputs != vk->num_public) return ZK_ERR_INVALID_WITNESS;
   if (!vk->ic_g1 || vk->ic_len < n_inputs + 1) {
     ctx->err = "verification key: ic_g1 shorter than the public inputs";
@@ -245,15 +256,24 @@ static int verify_many_run(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs,
   if (!n) return ZK_OK;
   hipStream_t st = ctx->stream;
   const size_t chunk = std::min<size_t>(ctx->verify_chunk, n), in_sz = sizeof(zk_fr) * n_inputs;
-  DevBuf d_vk, d_proofs, d_in, d_st;
+  DevBuf d_vk, d_proofs, d_in, d_st, d_bytes, d_pst;
   d_vk.ensure(4 * tables.size());
   d_proofs.ensure(sizeof(zk_proof) * chunk);
   d_in.ensure(std::max<size_t>(in_sz * chunk, 16));
   d_st.ensure(chunk);
+  if (bytes) {
+    d_bytes.ensure(192 * chunk);
+    d_pst.ensure(3 * chunk);
+  }
   ZK_HIP(hipMemcpyAsync(d_vk.p, tables.data(), 4 * tables.size(), hipMemcpyHostToDevice, st));
   for (size_t lo = 0; lo < n; lo += chunk) {
     const size_t m = std::min(chunk, n - lo);
-    ZK_HIP(hipMemcpyAsync(d_proofs.p, proofs + lo, sizeof(zk_proof) * m, hipMemcpyHostToDevice, st));
+    if (bytes) {
+      ZK_HIP(hipMemcpyAsync(d_bytes.p, bytes + 192 * lo, 192 * m, hipMemcpyHostToDevice, st));
+      proofs_decode_launch(ctx, st, d_bytes.as<uint8_t>(), m, d_proofs.as<uint64_t>(), d_pst.as<uint8_t>());
+    } else {
+      ZK_HIP(hipMemcpyAsync(d_proofs.p, proofs + lo, sizeof(zk_proof) * m, hipMemcpyHostToDevice, st));
+    }
     if (in_sz) ZK_HIP(hipMemcpyAsync(d_in.p, inputs + n_inputs * lo, in_sz * m, hipMemcpyHostToDevice, st));
     const int pi = ctx->prof.begin(st, "verify", m);
     if (sound)
@@ -265,6 +285,7 @@ static int verify_many_run(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs,
     ZK_LAUNCH_CHECK();
     ctx->prof.end(st, pi);
     ZK_HIP(hipMemcpyAsync(status + lo, d_st.p, m, hipMemcpyDeviceToHost, st));
+    if (point_status) ZK_HIP(hipMemcpyAsync(point_status + 3 * lo, d_pst.p, 3 * m, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));   // the next chunk reuses the buffers
   }
   if (ctx->prof.on) ctx->prof.collect();
@@ -317,12 +338,30 @@ using namespace zk;
 int zk_groth16_verify_many(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs, const zk_fr* public_inputs,
                            size_t n_inputs, size_t n_proofs, uint8_t* status) {
   if (!ctx || !vk || (n_proofs && (!proofs || !status || (n_inputs && !public_inputs)))) return ZK_ERR_ARG;
-  ZK_PGUARD(ctx, { return verify_many_run(ctx, vk, proofs, public_inputs, n_inputs, n_proofs, status, false); })
+  ZK_PGUARD(ctx, {
+    return verify_many_run(ctx, vk, proofs, nullptr, public_inputs, n_inputs, n_proofs, status, nullptr, false);
+  })
 }
 int zk_groth16_verify_many_sound(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs, const zk_fr* public_inputs,
                                  size_t n_inputs, size_t n_proofs, uint8_t* status) {
   if (!ctx || !vk || (n_proofs && (!proofs || !status || (n_inputs && !public_inputs)))) return ZK_ERR_ARG;
-  ZK_PGUARD(ctx, { return verify_many_run(ctx, vk, proofs, public_inputs, n_inputs, n_proofs, status, true); })
+  ZK_PGUARD(ctx, {
+    return verify_many_run(ctx, vk, proofs, nullptr, public_inputs, n_inputs, n_proofs, status, nullptr, true);
+  })
+}
+int zk_groth16_verify_many_bytes(zk_ctx* ctx, const zk_vk* vk, const uint8_t* proofs, const zk_fr* public_inputs,
+                                 size_t n_inputs, size_t n_proofs, uint8_t* status, uint8_t* point_status) {
+  if (!ctx || !vk || (n_proofs && (!proofs || !status || (n_inputs && !public_inputs)))) return ZK_ERR_ARG;
+  ZK_PGUARD(ctx, {
+    return verify_many_run(ctx, vk, nullptr, proofs, public_inputs, n_inputs, n_proofs, status, point_status, false);
+  })
+}
+int zk_groth16_verify_many_bytes_sound(zk_ctx* ctx, const zk_vk* vk, const uint8_t* proofs, const zk_fr* public_inputs,
+                                       size_t n_inputs, size_t n_proofs, uint8_t* status, uint8_t* point_status) {
+  if (!ctx || !vk || (n_proofs && (!proofs || !status || (n_inputs && !public_inputs)))) return ZK_ERR_ARG;
+  ZK_PGUARD(ctx, {
+    return verify_many_run(ctx, vk, nullptr, proofs, public_inputs, n_inputs, n_proofs, status, point_status, true);
+  })
 }
 int zk_pairing_products(zk_ctx* ctx, const zk_g1_affine* g1, const zk_g2_affine* g2, size_t pairs_per_product,
                         size_t n_products, uint8_t* status) {

@@ -1,7 +1,8 @@
 // points.hpp -- device helpers of point decompression and validation
 // (points.hip; the sqrt test hooks of testhooks.hip run the same functions):
 // square roots in Fq and Fq2, the sort-flag predicate of the zcash / ark
-// compressed encodings and the prime-order subgroup test, one lane per point.
+// compressed encodings and the prime-order subgroup tests ([r]P == O, and the
+// endomorphism criteria of the proof decoder), one lane per point.
 //
 // Everything here runs a few thousand field products per point in loops over
 // the bits of a fixed exponent or scalar.  The loops stay rolled and every
@@ -149,4 +150,59 @@ ZK_DI bool pt_in_subgroup(const Affine<F>& P) {
     if ((FR_MOD32[b >> 5] >> (b & 31)) & 1) acc = xyzz_madd(acc, P);
   }
   return xyzz_is_inf(acc);
+}
+
+// ---- subgroup by endomorphism (the proof decoder, points.hip) -------------------
+// Scott, "A note on group membership tests for G1, G2 and GT on BLS
+// pairing-friendly curves": for P on the curve, with x = -BLS_X_ABS,
+//   G1: P in G1 iff phi(P) = -[x^2] P,  phi(x, y) = (beta x, y)
+//   G2: P in G2 iff psi(P) = [x] P = -[|x|] P,  psi(x, y) = (conj(x) PSI_X, conj(y) PSI_Y)
+// (constants and their generator identities: gen_constants.py).  Equivalent
+// to [r]P == O above, with 2 x 63 (G1) / 63 (G2) doublings and 5 additions per
+// pass instead of 254 and 133.
+//
+// [|x|] B for B affine (mixed additions) or XYZZ (the second pass of G1,
+// whose base is the first pass's result): bit 63 of |x| is the start value,
+// the other 63 bits a rolled loop over the wave-uniform word.  The formulas'
+// own branches cover an accumulator meeting O, B or -B (small-order points).
+template <class F>
+ZK_DI XYZZ<F> pt_endo_start(const Affine<F>& b) { return xyzz_from_aff(b); }
+template <class F>
+ZK_DI XYZZ<F> pt_endo_start(const XYZZ<F>& b) { return b; }
+template <class F>
+ZK_DI XYZZ<F> pt_endo_add(const XYZZ<F>& a, const Affine<F>& b) { return xyzz_madd(a, b); }
+template <class F>
+ZK_DI XYZZ<F> pt_endo_add(const XYZZ<F>& a, const XYZZ<F>& b) { return xyzz_add(a, b); }
+template <class F, class B>
+__device__ __noinline__ XYZZ<F> pt_mul_x_abs(const B* base) {
+  static_assert(BLS_X_ABS >> 63, "the loop starts below the top bit of |x|");
+  XYZZ<F> acc = pt_endo_start(*base);
+#pragma unroll 1
+  for (int b = 62; b >= 0; b--) {
+    acc = xyzz_dbl(acc);
+    if ((BLS_X_ABS >> b) & 1) acc = pt_endo_add(acc, *base);
+  }
+  return acc;
+}
+// (px, py) == -Q without an inversion: px ZZ == X, py ZZZ == -Y, Q finite.
+// Q == O means "not in the subgroup": the affine P that reaches the test is
+// never the identity, and |x|, x^2 are not multiples of r.
+template <class F>
+ZK_DI bool pt_eq_neg(const F& px, const F& py, const XYZZ<F>& Q) {
+  if (xyzz_is_inf(Q)) return false;
+  return f_eq(f_mul(px, Q.ZZ), Q.X) && f_is_zero(f_add(f_mul(py, Q.ZZZ), Q.Y));
+}
+// P: on the curve, not the identity (as pt_in_subgroup)
+ZK_DI bool pt_in_subgroup_endo(const Affine<FqC>& P) {
+  const XYZZ<FqC> t = pt_mul_x_abs<FqC>(&P);
+  if (xyzz_is_inf(t)) return false;
+  const XYZZ<FqC> q = pt_mul_x_abs<FqC>(&t);   // [x^2] P
+  return pt_eq_neg(f_mul(P.x, FqC{fp_from_const<FqParams>(ENDO_BETA32)}), P.y, q);
+}
+ZK_DI bool pt_in_subgroup_endo(const Affine<Fq2C>& P) {
+  const XYZZ<Fq2C> q = pt_mul_x_abs<Fq2C>(&P);   // [|x|] P = -[x] P
+  const Fq2C cx = {{P.x.v.c0, fp_neg(P.x.v.c1)}}, cy = {{P.y.v.c0, fp_neg(P.y.v.c1)}};
+  const Fq2C kx = {{fp_from_const<FqParams>(ENDO_PSI_X32[0]), fp_from_const<FqParams>(ENDO_PSI_X32[1])}};
+  const Fq2C ky = {{fp_from_const<FqParams>(ENDO_PSI_Y32[0]), fp_from_const<FqParams>(ENDO_PSI_Y32[1])}};
+  return pt_eq_neg(f_mul(cx, kx), f_mul(cy, ky), q);
 }

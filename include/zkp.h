@@ -597,6 +597,47 @@ int zk_groth16_verify_many_bytes_sound(zk_ctx *ctx, const zk_vk *vk, const uint8
  * side of a pair contributes 1. */
 int zk_pairing_products(zk_ctx *ctx, const zk_g1_affine *g1, const zk_g2_affine *g2,
                         size_t pairs_per_product, size_t n_products, uint8_t *status);
+/* Sound batch verification: "are all n_proofs proofs valid?" for a sound key
+ * with ONE pairing check on the GPU (csrc/verify_all.hip).  With the explicit
+ * coefficients c_k = coeffs[k] (as zk_groth16_verify_batch takes them),
+ *   s = sum c_k, t_i = sum c_k x_{k,i} (mod r), IC* = s ic_g1[0] + sum t_i ic_g1[i+1],
+ *   prod_k e(c_k A_k, B_k) e(-s alpha, beta) e(-IC*, gamma) e(-sum c_k C_k, delta) == 1.
+ * *valid = 1 iff no proof is malformed and the check holds.  When every proof
+ * verifies the check holds for every choice of coefficients; when exactly one
+ * well-formed proof does not it fails for every choice; when several do not it
+ * fails except with probability about 2^-127 over independent uniform
+ * coefficients -- so draw them from a cryptographic generator, fresh per call
+ * and unknown to whoever made the proofs.  Each coefficient must be non-zero
+ * and below 2^128 (limbs 2 and 3 zero): else ZK_ERR_ARG, checked on the host
+ * before any GPU work, zk_last_error naming the index.  *first_malformed (may
+ * be NULL): the lowest index of a malformed proof, or n_proofs; any malformed
+ * proof makes *valid = 0.  Malformed is what
+ * zk_groth16_verify_many_bytes_sound calls MALFORMED -- range, curve,
+ * SUBGROUP, a public input >= r -- because the argument above needs A, B and C
+ * in the prime-order subgroup: unlike zk_groth16_verify_many this call runs
+ * the endomorphism subgroup test on the affine points.  A set infinity byte is
+ * the identity and is allowed; a pair with an infinite side contributes 1.
+ * Returns ZK_OK whenever a verdict was reached, whatever it is;
+ * n_inputs != vk->num_public -> ZK_ERR_INVALID_WITNESS; a malformed vk point or
+ * ic_len < n_inputs + 1 -> ZK_ERR_ARG (as zk_groth16_verify_many); NULL coeffs
+ * or valid with n_proofs > 0 -> ZK_ERR_ARG; a HIP error -> ZK_ERR_DEVICE;
+ * n_proofs == 0 -> *valid = 1.  The batch crosses the GPU in chunks of
+ * ZK_OPT_VERIFY_CHUNK proofs, the running accumulators staying on the device
+ * between chunks.  It does not say WHICH proof is invalid: a caller that needs
+ * that falls back to zk_groth16_verify_many_sound.  No reference counterpart:
+ * BatchVerifier's one-bit rule is no sound batching in any mode. */
+int zk_groth16_verify_all_sound(zk_ctx *ctx, const zk_vk *vk, const zk_proof *proofs,
+                                const zk_fr *public_inputs, size_t n_inputs, size_t n_proofs,
+                                const zk_fr *coeffs, int *valid, size_t *first_malformed);
+/* The same from wire bytes: proofs is n_proofs x 192 bytes, decoded and
+ * subgroup-checked by the proof decoder of zk_groth16_verify_many_bytes in the
+ * same call; malformed additionally covers the encoding.  point_status: 3 n
+ * bytes as in zk_proofs_deserialize_compressed (may be NULL).  The probability
+ * clause above applies; no reference counterpart. */
+int zk_groth16_verify_all_bytes_sound(zk_ctx *ctx, const zk_vk *vk, const uint8_t *proofs,
+                                      const zk_fr *public_inputs, size_t n_inputs, size_t n_proofs,
+                                      const zk_fr *coeffs, int *valid, size_t *first_malformed,
+                                      uint8_t *point_status);
 
 #ifdef __cplusplus
 }

@@ -83,6 +83,16 @@ int zk_test_fq12(zk_ctx *ctx, int op, const uint64_t *a, const uint64_t *b, size
  * then FINAL_EXP) as n Fq12 of 72 words.  Points must be canonical and on
  * their curves; an infinite point gives 1. */
 int zk_test_pairing_gt(zk_ctx *ctx, const zk_g1_affine *g1, const zk_g2_affine *g2, size_t n, uint64_t *out);
+/* The three folds of zk_groth16_verify_all_sound on their own: the same
+ * chunked Miller and fold path (ZK_OPT_VERIFY_CHUNK), then instead of the
+ * finish sum_c = S_C = sum c_k C_k in affine form, scal = the n_inputs + 1
+ * canonical scalars (s, t_0 .. t_{l-1}), and gt = FINAL_EXP of conj(F),
+ * F = prod f(c_k A_k, B_k), as 72 canonical words in zk_test_fq12's layout.
+ * Arguments and return codes as the product call; a malformed proof is
+ * ZK_ERR_ARG here. */
+int zk_test_verify_all_parts(zk_ctx *ctx, const zk_vk *vk, const zk_proof *proofs, const zk_fr *public_inputs,
+                             size_t n_inputs, size_t n_proofs, const zk_fr *coeffs, zk_g1_affine *sum_c,
+                             zk_fr *scal, uint64_t *gt);
 
 #ifdef __cplusplus
 }

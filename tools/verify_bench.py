@@ -31,6 +31,22 @@ proof_decode_g1 / proof_decode_g2 (the endomorphism subgroup test) against
 points_g1 / points_g2 ([r]P == O) on the same points, per point.
 
   python tools/verify_bench.py --bytes
+
+--all: sound batch verification (Context.verify_all_bytes,
+zk_groth16_verify_all_bytes_sound: one pairing check for the batch) against
+Context.verify_many_bytes(sound=True) (one verdict per proof) on the same
+bytes, alternating in one process, written to profiles/verify_all_bench.json.
+Two keys: the tool's own (num_public = 1, marked sound: its proofs satisfy the
+sound equation because every scalar is below 2^64) and a num_public = 3 key
+with full-width inputs whose proofs hold by construction -- the IC
+multiplications are what the batch check removes.  Whole calls (median), and
+at n = 262144 as well (the other sizes fit one wave per SIMD, where a call
+costs one lane's latency whatever it computes), and
+from one extra run of each under zk_ctx_profile the phases verify_all_miller,
+verify_all_fold, verify_all_finish against verify; the decode phases are the
+same kernels on both sides.
+
+  python tools/verify_bench.py --all
 """
 import argparse
 import importlib
@@ -137,20 +153,88 @@ def bytes_leg(zkp, ctx, vk, words, inputs, args, res):
         print("bytes_%d" % n, json.dumps(r), flush=True)
 
 
+def constructed_key(zkp, pyref, npub, count):
+    """a sound key and `count` proofs that satisfy the Groth16 equation by construction, with
+    full-width public inputs -> (vk, (count, 51) words, (count, npub, 4) inputs)"""
+    G1, G2, g1, g2, R = pyref.G1, pyref.G2, pyref.G1.gen, pyref.G2.gen, pyref.R
+    rng = pyref.SplitMix64(0xA11B)
+    al, be, ga, de = (rng.fr() for _ in range(4))
+    ks = [rng.fr() for _ in range(npub + 1)]
+    vk = zkp.VerificationKey.from_points(pyref.g1_words(G1.mul(g1, al)), pyref.g2_words(G2.mul(g2, be)),
+                                         pyref.g2_words(G2.mul(g2, ga)), pyref.g2_words(G2.mul(g2, de)),
+                                         [pyref.g1_words(G1.mul(g1, k)) for k in ks], sound=True)
+    words, inputs = [], []
+    for _ in range(count):
+        a, b = rng.fr(), rng.fr()
+        x = [rng.fr() for _ in range(npub)]
+        ic = (ks[0] + sum(xi * k for xi, k in zip(x, ks[1:]))) % R
+        c = (a * b - al * be - ic * ga) * pow(de, R - 2, R) % R
+        words.append(pyref.g1_words(G1.mul(g1, a)) + pyref.g2_words(G2.mul(g2, b)) + pyref.g1_words(G1.mul(g1, c)))
+        inputs.append([zkp.to_limbs(v) for v in x])
+    return vk, np.array(words, dtype=np.uint64), np.array(inputs, dtype=np.uint64).reshape(count, npub, 4)
+
+
+def all_leg(zkp, ctx, pyref, keys, args, res):
+    """verify_all_bytes against verify_many_bytes(sound=True) at every size, per key (module docstring)"""
+    rng = pyref.SplitMix64(0xC0EF)
+
+    def profiled(fn):
+        ctx.profile(1)
+        fn()
+        prof = ctx.profile_read()
+        ctx.profile(0)
+        return {ph: v["ms"] for ph, v in prof.items()}
+
+    for name, (vk, words, inputs) in keys.items():
+        recs = np.array([np.frombuffer(zkp.Proof(w).serialize_compressed(), dtype=np.uint8) for w in words])
+        for n in args.sizes:
+            reps = -(-n // len(words))
+            data = np.ascontiguousarray(np.tile(recs, (reps, 1))[:n])
+            inp = np.ascontiguousarray(np.tile(inputs, (reps, 1, 1))[:n])
+            co = np.zeros((n, 4), dtype=np.uint64)
+            co[:, 0] = [rng.next() | 1 for _ in range(n)]
+            co[:, 1] = [rng.next() for _ in range(n)]
+            assert ctx.verify_all_bytes(vk, data, inp, co) == (True, n)
+            assert (ctx.verify_many_bytes(vk, data, inp, sound=True) == zkp.ZK_VERIFY_ACCEPT).all()
+            wrong = inp.copy()
+            wrong[n // 2, 0, 0] ^= np.uint64(1)        # one wrong public input: the batch must reject
+            assert ctx.verify_all_bytes(vk, data, wrong, co) == (False, n)
+            t = timed_alternating({"all": lambda: ctx.verify_all_bytes(vk, data, inp, co),
+                                   "many": lambda: ctx.verify_many_bytes(vk, data, inp, sound=True)},
+                                  args.warmup, args.runs)
+            ka = profiled(lambda: ctx.verify_all_bytes(vk, data, inp, co))
+            km = profiled(lambda: ctx.verify_many_bytes(vk, data, inp, sound=True))
+            new = sum(ka.get(ph, 0.0) for ph in ("verify_all_miller", "verify_all_fold", "verify_all_finish"))
+            r = {"proofs": n, "num_public": int(vk.num_public), "verify_all_bytes": t["all"],
+                 "verify_many_bytes_sound": t["many"], "many_over_all": t["many"]["median_ms"] / t["all"]["median_ms"],
+                 "all_ms_per_proof": t["all"]["median_ms"] / n, "many_ms_per_proof": t["many"]["median_ms"] / n,
+                 "all_kernel_ms": ka, "many_kernel_ms": km, "all_new_phases_ms": new,
+                 "many_verify_phase_ms": km.get("verify", 0.0),
+                 "verify_phase_over_new_phases": km.get("verify", 0.0) / new if new else None,
+                 "new_phases_below_verify_phase": new < km.get("verify", 0.0)}
+            res["%s_%d" % (name, n)] = r
+            print("%s_%d" % (name, n), json.dumps(r), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--sizes", type=int, nargs="+", default=[1, 64, 4096, 65536])
+    ap.add_argument("--sizes", type=int, nargs="+", default=None,
+                    help="default 1 64 4096 65536; --all adds 262144 (four waves per SIMD: throughput, not latency)")
     ap.add_argument("--host-proofs", type=int, default=16)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--cpus", type=int, default=16)
     ap.add_argument("--bytes", action="store_true", help="the wire-bytes pipelines (module docstring)")
+    ap.add_argument("--all", action="store_true", help="sound batch verification against verify_many_bytes_sound")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "verify_bytes_bench.json" if args.bytes else "verify_bench.json")
+        args.out = os.path.join(ROOT, "profiles", "verify_all_bench.json" if args.all else
+                                "verify_bytes_bench.json" if args.bytes else "verify_bench.json")
     if args.runs < 5:
         ap.error("--runs must be at least 5")
+    if args.sizes is None:
+        args.sizes = [1, 64, 4096, 65536] + ([262144] if args.all else [])
 
     zkp = importlib.import_module("zero-knowledge-proofs_amd")
     import binding as oracle
@@ -191,9 +275,14 @@ def main():
     print("host_verify", json.dumps(r), flush=True)
 
     with zkp.Context(0) as ctx:
-        if args.bytes:
+        if args.all:
+            svk = zkp.VerificationKey.from_points(vk.point("alpha_g1"), vk.point("beta_g2"), vk.point("gamma_g2"),
+                                                  vk.point("delta_g2"), vk.ic_g1, sound=True)
+            all_leg(zkp, ctx, pyref, {"public1": (svk, words, inputs),
+                                      "public3": constructed_key(zkp, pyref, 3, len(words))}, args, res)
+        elif args.bytes:
             bytes_leg(zkp, ctx, vk, words, inputs, args, res)
-        for n in [] if args.bytes else args.sizes:
+        for n in [] if args.bytes or args.all else args.sizes:
             reps = -(-n // len(words))
             w = np.ascontiguousarray(np.tile(words, (reps, 1))[:n])
             inp = np.ascontiguousarray(np.tile(inputs, (reps, 1, 1))[:n])

@@ -60,11 +60,13 @@ EXPORTS = (
     "zk_groth16_verify_sound", "zk_groth16_verify_many_sound",
     "zk_msm_g1_upload_copies", "zk_msm_g2_upload_copies", "zk_pk_device_bytes",
     "zk_proofs_deserialize_compressed", "zk_groth16_verify_many_bytes", "zk_groth16_verify_many_bytes_sound",
+    "zk_groth16_verify_all_sound", "zk_groth16_verify_all_bytes_sound",
 )
 # include/zkp_test.h (libzkp_amd_test.so)
 TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fault_after_exchange",
                 "zk_test_pk_bases", "zk_test_pk_info", "zk_test_pk_plan", "zk_test_fq_sqrt", "zk_test_fq2_sqrt",
-                "zk_test_fq12", "zk_test_pairing_gt", "zk_test_fixed_base_g1", "zk_test_fixed_base_g2")
+                "zk_test_fq12", "zk_test_pairing_gt", "zk_test_fixed_base_g1", "zk_test_fixed_base_g2",
+                "zk_test_verify_all_parts")
 ZK_OPT_QUOTIENT_PATH, ZK_OPT_PROVE_WIN_C, ZK_OPT_EXCHANGE_TIMEOUT_MS, ZK_OPT_DIST_QUOTIENT = 1, 2, 3, 5
 ZK_OPT_EXCHANGE_FIRST = 6
 ZK_OPT_POINT_CHUNK = 7
@@ -624,6 +626,74 @@ class Context:
                 _p(pst) if n and point_status else None)
         _check(rc, self, "zk_groth16_verify_many_bytes")
         return (st, pst) if point_status else st
+
+    @staticmethod
+    def _coeffs(coeffs, n):
+        co = _fr_rows(coeffs) if n else np.zeros((0, 4), dtype=np.uint64)
+        if len(co) != n:
+            raise ValueError("verify_all: one coefficient per proof")
+        return co
+
+    def verify_all(self, vk, proofs, inputs, coeffs):
+        """zk_groth16_verify_all_sound: ONE pairing check for n proofs (as
+        verify_many takes them) against a sound vk, with the coefficients
+        c_k (ints or (n, 4) words; non-zero, below 2^128) of the random linear
+        combination -> (valid, first_malformed): valid iff no proof is
+        malformed (range, curve, subgroup, an input >= r) and the combined
+        check holds; first_malformed the lowest malformed index, or n.  With
+        several invalid proofs the check passes with probability ~2^-127 over
+        uniform coefficients: draw them with `secrets` (Verifier.verify_all
+        does).  ValueError for a bad coefficient, InvalidWitness when
+        n_inputs != vk.num_public."""
+        if isinstance(proofs, np.ndarray):
+            pw = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, PROOF_WORDS)
+        else:
+            pw = np.ascontiguousarray([p.words for p in proofs], dtype=np.uint64).reshape(-1, PROOF_WORDS)
+        n = len(pw)
+        inp = self._verify_inputs(vk, inputs, n)
+        co = self._coeffs(coeffs, n)
+        valid, first = C.c_int(0), C.c_size_t(0)
+        rc = lib().zk_groth16_verify_all_sound(
+            C.c_void_p(self._h), C.byref(vk.s), _p(pw) if n else None, _p(inp) if inp.size else None,
+            C.c_size_t(inp.shape[1]), C.c_size_t(n), _p(co) if n else None, C.byref(valid), C.byref(first))
+        _check(rc, self, "zk_groth16_verify_all_sound")
+        return bool(valid.value), int(first.value)
+
+    def verify_all_bytes(self, vk, data, inputs, coeffs, point_status=False):
+        """zk_groth16_verify_all_bytes_sound: verify_all on n compressed
+        proofs (bytes, or an (n, 192) uint8 array), decoded and
+        subgroup-checked on the GPU in the same call -> (valid,
+        first_malformed), with point_status also the (n, 3) zk_point_status
+        of a, b, c."""
+        buf, n = self._proof_bytes(data, "verify_all_bytes")
+        inp = self._verify_inputs(vk, inputs, n)
+        co = self._coeffs(coeffs, n)
+        pst = np.zeros((n, 3), dtype=np.uint8)
+        valid, first = C.c_int(0), C.c_size_t(0)
+        rc = lib().zk_groth16_verify_all_bytes_sound(
+            C.c_void_p(self._h), C.byref(vk.s), _p(buf) if n else None, _p(inp) if inp.size else None,
+            C.c_size_t(inp.shape[1]), C.c_size_t(n), _p(co) if n else None, C.byref(valid), C.byref(first),
+            _p(pst) if n and point_status else None)
+        _check(rc, self, "zk_groth16_verify_all_bytes_sound")
+        out = (bool(valid.value), int(first.value))
+        return out + (pst,) if point_status else out
+
+    def test_verify_all_parts(self, vk, proofs, inputs, coeffs):
+        """zk_test_verify_all_parts (test library): the three folds of
+        verify_all -> (S_C as 13 affine words, the n_inputs + 1 scalars
+        (s, t_0 ..) as ints, FINAL_EXP(conj(F)) as 72 words)."""
+        pw = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, PROOF_WORDS)
+        n = len(pw)
+        inp = self._verify_inputs(vk, inputs, n)
+        co = self._coeffs(coeffs, n)
+        sum_c = np.zeros(G1_WORDS, dtype=np.uint64)
+        scal = np.zeros((inp.shape[1] + 1, 4), dtype=np.uint64)
+        gt = np.zeros(FQ12_WORDS, dtype=np.uint64)
+        rc = test_lib().zk_test_verify_all_parts(
+            C.c_void_p(self._h), C.byref(vk.s), _p(pw) if n else None, _p(inp) if inp.size else None,
+            C.c_size_t(inp.shape[1]), C.c_size_t(n), _p(co) if n else None, _p(sum_c), _p(scal), _p(gt))
+        _check(rc, self, "zk_test_verify_all_parts")
+        return sum_c, [sum(int(w) << (64 * i) for i, w in enumerate(row)) for row in scal], gt
 
     def test_fixed_base(self, scalars, g2=False):
         """zk_test_fixed_base_g1 / _g2 (test library): scalars (ints, or (n, 4)
@@ -1520,6 +1590,65 @@ class Verifier:
         return st == ZK_VERIFY_ACCEPT
 
 
+    @staticmethod
+    def _all_args(vk, proofs_and_inputs, coeffs, what):
+        if not getattr(vk, "sound", False):
+            raise ValueError(f"{what}: sound keys only (the reference mode has no sound batching, DESIGN.md 2.9)")
+        rows = [_fr_rows(inp) for _, inp in proofs_and_inputs]
+        if any(len(r) != vk.num_public for r in rows):
+            raise InvalidWitness(f"{what}: a proof's public inputs do not match vk.num_public")
+        inp = np.zeros((len(rows), vk.num_public, 4), dtype=np.uint64)
+        for k, r in enumerate(rows):
+            inp[k] = r
+        if coeffs is None:
+            import secrets
+            coeffs = []
+            for _ in rows:
+                c = 0
+                while not c:      # uniform on [1, 2^128)
+                    c = secrets.randbits(128)
+                coeffs.append(c)
+        return inp, coeffs
+
+    @staticmethod
+    def verify_all(vk, proofs_and_inputs, ctx=None, coeffs=None):
+        """"Are all n proofs valid?" for a sound vk with one pairing check on
+        the GPU (Context.verify_all) -> bool.  coeffs=None draws one non-zero
+        128-bit coefficient per proof from `secrets`: a batch with invalid
+        proofs then passes with probability ~2^-127 at most, and a batch with
+        exactly one never.  It does not say which proof is invalid
+        (verify_many does).  ValueError naming the first malformed proof
+        (which here includes a point outside the prime-order subgroup),
+        InvalidWitness on an input-count mismatch, ValueError for a vk that
+        is not sound."""
+        ctx = ctx or default_context()
+        inp, coeffs = Verifier._all_args(vk, proofs_and_inputs, coeffs, "verify_all")
+        valid, bad = ctx.verify_all(vk, [p for p, _ in proofs_and_inputs], inp, coeffs)
+        if bad < len(proofs_and_inputs):
+            raise ValueError(f"verify_all: proof {bad} has a point that is not canonical or not on its curve"
+                             ", or a public input that is not below r, or a point outside the prime-order subgroup")
+        return valid
+
+    @staticmethod
+    def verify_all_bytes(vk, proofs_and_inputs, ctx=None, coeffs=None):
+        """verify_all on compressed proofs: n pairs (192 bytes, public inputs)
+        -> bool.  ValueError naming the first malformed proof, its failing
+        point and why, as verify_many_bytes."""
+        ctx = ctx or default_context()
+        inp, coeffs = Verifier._all_args(vk, proofs_and_inputs, coeffs, "verify_all_bytes")
+        if any(len(b) != PROOF_BYTES for b, _ in proofs_and_inputs):
+            raise ValueError(f"verify_all_bytes: a compressed Proof is {PROOF_BYTES} bytes")
+        valid, k, pst = ctx.verify_all_bytes(vk, b"".join(bytes(b) for b, _ in proofs_and_inputs), inp, coeffs,
+                                             point_status=True)
+        if k < len(proofs_and_inputs):
+            pts = np.flatnonzero(pst[k])
+            if len(pts):
+                j = int(pts[0])
+                raise ValueError(f"verify_all_bytes: proof {k} point {'abc'[j]}: {POINT_STATUS_TEXT[pst[k][j]]}")
+            raise ValueError(f"verify_all_bytes: proof {k} has a public input that is not below r")
+        return valid
+
+
 class BatchVerifier:
     """BatchVerifier::verify_batch (core:360-432).  The reference draws one
     Fr::rand coefficient per proof; pass them as `coeffs` (or an `rng`
@@ -1529,7 +1658,8 @@ class BatchVerifier:
     def verify_batch(vk, proofs_and_inputs, coeffs=None, rng=None):
         if getattr(vk, "sound", False):
             # the reference's one-bit rule is no sound batching in any mode
-            raise ValueError("BatchVerifier is reference-only: verify a sound key's proofs with Verifier.verify_many")
+            raise ValueError("BatchVerifier is reference-only: verify a sound key's proofs with Verifier.verify_all "
+                             "(one verdict for the batch) or Verifier.verify_many (one per proof)")
         k = len(proofs_and_inputs)
         if coeffs is None:
             if k and rng is None:

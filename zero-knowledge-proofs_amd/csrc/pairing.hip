@@ -20,61 +20,16 @@
 #include "ctx.hpp"
 #include "host_pairing.hpp"
 #include "pairing.hpp"
+#include "verify_all.hpp"
 
 namespace zk {
 
-constexpr int PR_BLOCK = 64;
-constexpr size_t PROOF_WORDS = sizeof(zk_proof) / 8, G1W = sizeof(zk_g1_affine) / 8, G2W = sizeof(zk_g2_affine) / 8;
-static_assert(PROOF_WORDS == 51 && G1W == 13 && G2W == 25, "ABI point sizes");
 // the per-call words of a verification key (32-bit, device Montgomery):
 //   [VK_AB, +144)                   the Miller value of (-alpha, beta), tower order
 //   [VK_TAB, +2 x 48 PR_STEPS)      the lines of gamma, then of delta
 //   [VK_ON, +4)                     gamma finite, delta finite
 //   [VK_IC, +24 (n_inputs + 1))     ic_g1: x, y; an identity entry is (0, 0)
 constexpr size_t VK_AB = 0, VK_TAB = 144, VK_ON = VK_TAB + 2 * 48 * PR_STEPS, VK_IC = VK_ON + 4;
-
-ZK_DI void pr_use_g1(PrPairs& in, int j, const Affine<FqC>& P, bool on) {
-  in.on[j] = on;
-  in.xp[j] = P.x.v;
-  in.yp[j] = P.y.v;
-}
-
-// k P for a 64-bit k: double-and-add from the top bit, mixed additions
-static __device__ __noinline__ XYZZ<FqC> pr_g1_mul64(const Affine<FqC>* P, uint64_t k) {
-  XYZZ<FqC> t;
-  xyzz_set_inf(t);
-#pragma unroll 1
-  for (int b = 63; b >= 0; b--) {
-    t = xyzz_dbl(t);
-    if ((k >> b) & 1) t = xyzz_madd(t, *P);
-  }
-  return t;
-}
-// k P for a whole scalar k < r (sound mode): k = 4 u64 limbs in device memory,
-// 255 bits from the top, the same rolled double-and-add
-static __device__ __noinline__ XYZZ<FqC> pr_g1_mul255(const Affine<FqC>* P, const uint64_t* k) {
-  XYZZ<FqC> t;
-  xyzz_set_inf(t);
-#pragma unroll 1
-  for (int b = 254; b >= 0; b--) {
-    t = xyzz_dbl(t);
-    if ((k[b >> 6] >> (b & 63)) & 1) t = xyzz_madd(t, *P);
-  }
-  return t;
-}
-// a 4-limb public input is a reduced Fr (< r)
-static __device__ __forceinline__ bool pr_fr_reduced(const uint64_t* k) {
-#pragma unroll
-  for (int i = 3; i >= 0; i--)
-    if (k[i] != FR_MOD64[i]) return k[i] < FR_MOD64[i];
-  return false;
-}
-// x = X / ZZ, y = Y / ZZZ with one inversion: 1 / ZZ = (ZZ / ZZZ)^2
-ZK_DI Affine<FqC> pr_g1_affine(const XYZZ<FqC>& p) {
-  const FqC i3 = {pr_fq_inv(p.ZZZ.v)};
-  const FqC i2 = f_sqr(f_mul(p.ZZ, i3));
-  return {f_mul(p.X, i2), f_mul(p.Y, i3)};
-}
 
 // One lane per proof: Verifier::verify (verify.hip's zk_groth16_verify) with
 // the four Miller loops sharing their squarings.  SOUND
@@ -170,7 +125,7 @@ __global__ void __launch_bounds__(PR_BLOCK) k_pairing_products(const uint64_t* _
 }
 
 // ---- per-call data (host) ------------------------------------------------------
-static void put_fq(uint32_t* out, const host::Fq& m) {
+void put_fq(uint32_t* out, const host::Fq& m) {
   const host::Fq d = host::to_dev(m);
   std::memcpy(out, d.l, 48);
 }
@@ -180,7 +135,7 @@ static void put_fq2(uint32_t* out, const host::Fq2& m) {
 }
 // The slopes of host_pairing.hpp's miller_loop for Q, step by step: lambda'
 // and lambda' x' - y' (line_eval's c0.c0), 48 words per step.
-static void line_table(const host::A2& Q, uint32_t* out) {
+void line_table(const host::A2& Q, uint32_t* out) {
   host::Fq2 tx = Q.x, ty = Q.y;
   int step = 0;
   for (int i = 62; i >= 0; i--) {

@@ -10,6 +10,7 @@
 #include "points.hpp"
 #include "prove.hpp"
 #include "setup.hpp"
+#include "verify_all.hpp"
 #include "../../include/zkp_test.h"
 
 using namespace zk;
@@ -271,6 +272,67 @@ int zk_test_pairing_gt(zk_ctx* ctx, const zk_g1_affine* g1, const zk_g2_affine* 
     k_test_pairing_gt<<<ceil_div(n, 64), 64, 0, st>>>(d_g1.as<uint64_t>(), d_g2.as<uint64_t>(), n, d_out.as<uint64_t>());
     ZK_LAUNCH_CHECK();
     ZK_HIP(hipMemcpyAsync(out, d_out.p, 8 * 72 * n, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    return ZK_OK;
+  })
+}
+
+// ---- the three folds of the sound batch check on their own --------------------
+namespace zk {
+// one lane on the accumulators (slot 0) that verify_all_accumulate leaves
+__global__ void __launch_bounds__(64) k_test_verify_all_parts(const F12* __restrict__ F, const XYZZ<FqC>* __restrict__ g,
+                                                              const Fr* __restrict__ s, size_t W,
+                                                              uint64_t* __restrict__ sum_c, uint64_t* __restrict__ scal,
+                                                              uint64_t* __restrict__ gt) {
+  if (blockIdx.x || threadIdx.x) return;
+  F12 f = F[0];
+  f12_conj(&f, &f);
+  f12_final_exp(&f);
+  t_write_f12(gt, &f);
+  const XYZZ<FqC> sc = g[0];
+  const bool inf = xyzz_is_inf(sc);
+  Affine<FqC> P;
+  f_set_zero(P.x);
+  f_set_zero(P.y);
+  if (!inf) P = pr_g1_affine(sc);
+  pr_write_fq(sum_c, inf ? P.x.v : pt_from_mont(P.x.v));
+  pr_write_fq(sum_c + 6, inf ? P.y.v : pt_from_mont(P.y.v));
+  sum_c[12] = inf ? 1 : 0;
+#pragma unroll 1
+  for (size_t j = 0; j < W; j++) {
+    const Fr c = fp_from_mont(s[j]);
+#pragma unroll
+    for (int k = 0; k < 4; k++) scal[4 * j + k] = (uint64_t)c.v[2 * k] | ((uint64_t)c.v[2 * k + 1] << 32);
+  }
+}
+}  // namespace zk
+
+int zk_test_verify_all_parts(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs, const zk_fr* public_inputs,
+                             size_t n_inputs, size_t n_proofs, const zk_fr* coeffs, zk_g1_affine* sum_c, zk_fr* scal,
+                             uint64_t* gt) {
+  if (!ctx || !vk || !sum_c || !scal || !gt || (n_proofs && (!proofs || !coeffs || (n_inputs && !public_inputs))))
+    return ZK_ERR_ARG;
+  ZK_TGUARD(ctx, {
+    VerifyAll S;
+    size_t first_bad = n_proofs;
+    const int rc = verify_all_accumulate(ctx, vk, proofs, nullptr, public_inputs, n_inputs, n_proofs, coeffs,
+                                         &first_bad, nullptr, S);
+    if (ctx->prof.on) ctx->prof.collect();
+    if (rc != ZK_OK) return rc;
+    if (first_bad < n_proofs) {
+      ctx->err = "proof " + std::to_string(first_bad) + " is malformed";
+      return ZK_ERR_ARG;
+    }
+    const size_t W = S.W;
+    DevBuf d_out;
+    d_out.ensure(8 * (13 + 4 * W + 72));
+    uint64_t* o = d_out.as<uint64_t>();
+    hipStream_t st = ctx->stream;
+    k_test_verify_all_parts<<<1, 64, 0, st>>>(S.F(), S.G(), S.S(), W, o, o + 13, o + 13 + 4 * W);
+    ZK_LAUNCH_CHECK();
+    ZK_HIP(hipMemcpyAsync(sum_c, o, 8 * 13, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipMemcpyAsync(scal, o + 13, 32 * W, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipMemcpyAsync(gt, o + 13 + 4 * W, 8 * 72, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));
     return ZK_OK;
   })

@@ -177,8 +177,8 @@ int zk_ctx_set_schedule(zk_ctx *ctx, int schedule);
  *                         effect without a distributed quotient or under
  *                         schedule 3, where everything runs in order)
  *   ZK_OPT_POINT_CHUNK    points per kernel launch and device buffer of the
- *                         point decompression / validation calls (default
- *                         2^20, >= 1)
+ *                         point decompression / validation calls and of
+ *                         zk_g1_mul_scalar (default 2^20, >= 1)
  *   ZK_OPT_VERIFY_CHUNK   proofs (products) per kernel launch and device
  *                         buffer of zk_groth16_verify_many /
  *                         zk_pairing_products (default 65536: one lane per
@@ -638,6 +638,78 @@ int zk_groth16_verify_all_bytes_sound(zk_ctx *ctx, const zk_vk *vk, const uint8_
                                       const zk_fr *public_inputs, size_t n_inputs, size_t n_proofs,
                                       const zk_fr *coeffs, int *valid, size_t *first_malformed,
                                       uint8_t *point_status);
+
+/* ------------------------------------------- phase-2 key contributions --- */
+/* Sound keys only.  A key from zk_groth16_setup_sound is known to whoever held
+ * its five parameters; the phase-2 step of a Groth16 ceremony removes that for
+ * delta: each participant multiplies delta by a secret share d of their own,
+ * anyone checks that the new key is the old one with only delta changed, and
+ * the key is safe if a single participant forgot their share.  With
+ * e = 1 / d mod r, by the sound-mode formulas above,
+ *   delta_g1 <- d delta_g1, delta_g2 <- d delta_g2 (pk and vk: the same point)
+ *   ic_g1[i] <- e ic_g1[i] (pk), h_g1[i] <- e h_g1[i]
+ * and alpha_g1, beta_g1, beta_g2, a_g1, b_g1, b_g2, num_public, the vk's
+ * gamma_g2 and the vk's ic_g1 (which is over gamma) stay: entry for entry the
+ * key zk_groth16_setup_sound gives for delta d mod r in place of delta.  A
+ * reference-mode key cannot be rescaled (its h_g1[i] = [lo64(tau~^i / delta~)]_1
+ * is not linear in 1 / delta); the structs carry no mode flag, so the _sound
+ * suffix is the caller's statement of mode, as with zk_pk_upload_sound.  No
+ * reference counterpart: the reference's `ceremony` (setup:282-352) works over
+ * its truncated scalars.
+ *
+ * out[i] = k pts[i] for n G1 points and ONE scalar, on the GPU, one lane per
+ * point (csrc/ceremony.hip: a joint 128-bit walk over P and its endomorphism
+ * image).  Canonical affine words out; a set infinity byte gives the identity
+ * (zero coordinates, infinity byte 1), k = 0 gives n identities.  k >= r ->
+ * ZK_ERR_ARG; n == 0 -> ZK_OK; out == pts (in place) is allowed.  The points
+ * are ASSUMED canonical, on the curve and in the prime-order subgroup -- for
+ * others the result is unspecified; a caller who does not know that runs
+ * zk_g1_validate first, as for zk_pk_upload.  The array crosses the GPU in
+ * chunks of ZK_OPT_POINT_CHUNK points; after ZK_ERR_DEVICE the chunks already
+ * done are in out (in place: a caller who must keep the input works on a copy,
+ * as zk_groth16_contribute_sound does). */
+int zk_g1_mul_scalar(zk_ctx *ctx, const zk_g1_affine *pts, size_t n, const zk_fr *k,
+                     zk_g1_affine *out);
+/* One contribution with the share d, in place on a HOST key; vk may be NULL,
+ * else its delta_g2 must be pk's (ZK_ERR_ARG) and is replaced with it.  d = 0
+ * or d >= r -> ZK_ERR_ARG, checked before any GPU work.  The two delta points
+ * go through the host curve code, ic_g1 and h_g1 through zk_g1_mul_scalar's
+ * kernel with 1 / d.  On any error the key is exactly as it was.  Device keys
+ * (zk_pk_dev) are not rescaled in place: a caller uploads the new host key
+ * (zk_pk_upload_sound). */
+int zk_groth16_contribute_sound(zk_ctx *ctx, zk_pk *pk, zk_vk *vk, const zk_fr *d);
+/* Is (after, vk_after) a contribution on top of (before, vk_before)?  Returns
+ * ZK_OK whenever a verdict was reached; *status is the first check that fails:
+ *   SHAPE       array lengths or num_public differ, or n_coeffs != h_len + ic_len
+ *   FIXED_PART  alpha_g1, beta_g1, beta_g2, a_g1, b_g1, b_g2 or the vk's
+ *               alpha_g1, beta_g2, gamma_g2, ic_g1 differ byte for byte (struct
+ *               padding excluded); or a vk's delta_g2 is not its pk's
+ *   POINT       after's delta_g1, delta_g2 or an ic_g1 / h_g1 entry fails
+ *               zk_g1_validate / zk_g2_validate (the subgroup matters: the
+ *               pairing checks below say nothing about cofactor parts);
+ *               zk_last_error names the array and the index
+ *   DELTA       a new delta point is the identity, or
+ *               e(delta_1', delta_2) e(-delta_1, delta_2') != 1 -- the product
+ *               is 1 exactly when G1 and G2 got the same share
+ *   RATIO       with S = sum rho_i h_g1[i] + sum rho_{h_len + j} ic_g1[j] over the
+ *               old key and S' over the new one (two 255-bit MSMs),
+ *               e(S', delta_2') e(-S, delta_2) != 1
+ * rho = coeffs, as in zk_groth16_verify_all_sound: each non-zero and below
+ * 2^128, else ZK_ERR_ARG (after the SHAPE check; zk_last_error names the
+ * index).  An honest contribution passes for every choice; a key with a
+ * rescaled entry off by a non-zero subgroup element fails except with
+ * probability about 2^-127 over independent uniform coefficients -- draw them
+ * from a cryptographic generator, fresh per call.  The old key is the caller's
+ * own and is not validated (a malformed point of it is ZK_ERR_ARG at best).
+ * OUT OF SCOPE: a proof that the contributor knows d.  A public transcript
+ * needs one for its security proof, and it needs a hash to G2.  What this call
+ * establishes is that the new key is a well-formed sound key for some delta'
+ * related to the old delta. */
+typedef enum { ZK_CONTRIB_OK = 0, ZK_CONTRIB_SHAPE, ZK_CONTRIB_FIXED_PART,
+               ZK_CONTRIB_POINT, ZK_CONTRIB_DELTA, ZK_CONTRIB_RATIO } zk_contribution_status;
+int zk_groth16_verify_contribution_sound(zk_ctx *ctx, const zk_pk *before, const zk_vk *vk_before,
+                                         const zk_pk *after, const zk_vk *vk_after,
+                                         const zk_fr *coeffs, size_t n_coeffs, int *status);
 
 #ifdef __cplusplus
 }

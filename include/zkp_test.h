@@ -58,6 +58,12 @@ int zk_test_pk_plan(const zk_pk_dev *pk, uint32_t *copies, uint32_t *sets);
 int zk_test_fixed_base_g1(zk_ctx *ctx, const zk_fr *scalars, size_t n, zk_g1_affine *out);
 /* Same with the G2 generator. */
 int zk_test_fixed_base_g2(zk_ctx *ctx, const zk_fr *scalars, size_t n, zk_g2_affine *out);
+/* zk_g1_mul_scalar through the plain 255-bit double-and-add walk
+ * (csrc/ceremony.hpp, cm_walk_plain) instead of the endomorphism walk the
+ * library ships: the on-GPU cross-check of that walk and its timing baseline
+ * (profiler phase g1_mul_scalar_plain).  Same arguments, errors and chunking. */
+int zk_test_g1_mul_scalar_plain(zk_ctx *ctx, const zk_g1_affine *pts, size_t n, const zk_fr *k,
+                                zk_g1_affine *out);
 /* The device square roots behind point decompression (csrc/points.hpp), one
  * lane per element: in = n canonical Fq (6 words each), out = a canonical
  * root where ok[i] = 1 (zeros where the input has none), largest[i] = the

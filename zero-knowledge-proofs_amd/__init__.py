@@ -61,12 +61,13 @@ EXPORTS = (
     "zk_msm_g1_upload_copies", "zk_msm_g2_upload_copies", "zk_pk_device_bytes",
     "zk_proofs_deserialize_compressed", "zk_groth16_verify_many_bytes", "zk_groth16_verify_many_bytes_sound",
     "zk_groth16_verify_all_sound", "zk_groth16_verify_all_bytes_sound",
+    "zk_g1_mul_scalar", "zk_groth16_contribute_sound", "zk_groth16_verify_contribution_sound",
 )
 # include/zkp_test.h (libzkp_amd_test.so)
 TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fault_after_exchange",
                 "zk_test_pk_bases", "zk_test_pk_info", "zk_test_pk_plan", "zk_test_fq_sqrt", "zk_test_fq2_sqrt",
                 "zk_test_fq12", "zk_test_pairing_gt", "zk_test_fixed_base_g1", "zk_test_fixed_base_g2",
-                "zk_test_verify_all_parts")
+                "zk_test_verify_all_parts", "zk_test_g1_mul_scalar_plain")
 ZK_OPT_QUOTIENT_PATH, ZK_OPT_PROVE_WIN_C, ZK_OPT_EXCHANGE_TIMEOUT_MS, ZK_OPT_DIST_QUOTIENT = 1, 2, 3, 5
 ZK_OPT_EXCHANGE_FIRST = 6
 ZK_OPT_POINT_CHUNK = 7
@@ -85,6 +86,9 @@ ZK_POINT_OK, ZK_POINT_ENCODING, ZK_POINT_NOT_CANONICAL, ZK_POINT_NOT_ON_CURVE, Z
 POINT_STATUS_TEXT = ("valid", "bad encoding flags", "coordinate not below p", "not on the curve",
                      "not in the prime-order subgroup")
 G1_BYTES, G2_BYTES = 48, 96
+# zk_contribution_status: the first check of CRS.verify_contribution that fails
+(ZK_CONTRIB_OK, ZK_CONTRIB_SHAPE, ZK_CONTRIB_FIXED_PART, ZK_CONTRIB_POINT, ZK_CONTRIB_DELTA,
+ ZK_CONTRIB_RATIO) = range(6)
 PROOF_BYTES, PROOF_WORDS = 192, 51
 CSRC = os.path.join(_HERE, "csrc")
 
@@ -403,6 +407,12 @@ class Context:
         _check(lib().zk_ctx_attach_exchange(C.c_void_p(self._h), C.byref(ops), C.c_int(rank), C.c_int(world)), self,
                "zk_ctx_attach_exchange")
 
+    def last_error(self):
+        """zk_last_error: the detail text of the ctx's last failed call (or
+        of a verdict that names a point, as CRS.verify_contribution's POINT)."""
+        msg = lib().zk_last_error(self._h)
+        return msg.decode() if msg else ""
+
     def set_schedule(self, schedule=-1):
         """zk_ctx_set_schedule: -1 / 0 overlapped streams (default), 3 every
         prove kernel in order on one stream (isolated kernel durations)."""
@@ -418,7 +428,7 @@ class Context:
         (-1 distributed when an exchange of the key's shape is attached, 0
         replicated), ZK_OPT_EXCHANGE_FIRST (0 MSMs start with the witness, 1
         they wait for the distributed quotient), ZK_OPT_POINT_CHUNK (points
-        per launch of the decompress / validate calls, >= 1) or
+        per launch of the decompress / validate / g1_mul_scalar calls, >= 1) or
         ZK_OPT_VERIFY_CHUNK (proofs / products per launch of verify_many /
         pairing_products, default 65536, >= 1).  Explicit path choices for
         tests and A/B runs."""
@@ -545,6 +555,30 @@ class Context:
     def g2_validate(self, arr):
         """zk_g2_validate: (n, 25) affine words -> n statuses."""
         return self._validate("zk_g2_validate", arr, G2_WORDS)
+
+    # ---- n G1 points times one scalar (phase-2 key contributions) ----
+    def _g1_mul_scalar(self, fn, name, points, k):
+        a = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, G1_WORDS)
+        k = int(k)
+        if k < 0 or k >> 256:
+            raise ValueError(f"{name}: the scalar must be in [0, r)")
+        kw = np.array(to_limbs(k), dtype=np.uint64)   # whole: a scalar >= r is the library's error
+        out = np.zeros_like(a)
+        _check(fn(C.c_void_p(self._h), _p(a) if len(a) else None, C.c_size_t(len(a)), _p(kw),
+                  _p(out) if len(a) else None), self, name)
+        return out
+
+    def g1_mul_scalar(self, points, k):
+        """zk_g1_mul_scalar: (n, 13) affine words and one scalar 0 <= k < r ->
+        (n, 13) words of k * point, one lane per point.  The points are taken
+        as canonical, on the curve and in the prime-order subgroup
+        (g1_validate checks that).  ValueError for k >= r."""
+        return self._g1_mul_scalar(lib().zk_g1_mul_scalar, "zk_g1_mul_scalar", points, k)
+
+    def test_g1_mul_scalar_plain(self, points, k):
+        """zk_test_g1_mul_scalar_plain (test library): g1_mul_scalar through
+        the plain 255-bit double-and-add walk."""
+        return self._g1_mul_scalar(test_lib().zk_test_g1_mul_scalar_plain, "zk_test_g1_mul_scalar_plain", points, k)
 
     # ---- batch verification on the GPU (one lane per proof / product) ----
     @staticmethod
@@ -1280,6 +1314,72 @@ class CRS:
     @classmethod
     def generate_random(cls, ctx, qap, num_public, rng, sound=False):
         return cls.generate_from_qap(ctx, qap, SetupParams.random(rng), num_public, sound)
+
+    # ---- phase-2 contributions (sound keys) ----
+    def copy(self):
+        """A CRS with arrays and points of its own."""
+        pk, vk = self.pk, self.vk
+        npk = ProvingKey(len(pk.a_g1), len(pk.h_g1), pk.num_public, pk.qap, pk.sound)
+        for nm in ("a_g1", "b_g1", "b_g2", "ic_g1", "h_g1"):
+            setattr(npk, nm, np.array(getattr(pk, nm), dtype=np.uint64, copy=True))
+        for nm, _, single in _PK_FIELDS:
+            if single:
+                setattr(npk.s, nm, type(getattr(pk.s, nm)).from_buffer_copy(getattr(pk.s, nm)))
+        nvk = VerificationKey.from_points(vk.point("alpha_g1"), vk.point("beta_g2"), vk.point("gamma_g2"),
+                                          vk.point("delta_g2"), vk.ic_g1, vk.sound)
+        return CRS(npk, nvk)
+
+    def contribute(self, ctx, d):
+        """zk_groth16_contribute_sound: one phase-2 contribution with the
+        secret share 0 < d < r -> a NEW CRS (this one is left untouched):
+        delta_g1 and delta_g2 times d, every pk ic_g1 and h_g1 entry times
+        1 / d on the GPU, everything else as it was -- the key
+        generate_from_qap(sound=True) gives for delta * d.  SetupError for a
+        reference-mode key (its h_g1 is not linear in 1 / delta) or a bad
+        share.  A device key is not rescaled: upload the new one."""
+        if not (self.pk.sound and self.vk.sound):
+            raise SetupError("contribute: sound keys only (a reference-mode key cannot be rescaled)")
+        d = int(d)
+        if not 0 < d < R:
+            raise SetupError("contribute: the share must be in (0, r)")
+        new = self.copy()
+        rc = lib().zk_groth16_contribute_sound(C.c_void_p(ctx._h), C.byref(new.pk._bind()), C.byref(new.vk.s),
+                                               C.byref(_fr(d)))
+        if rc == ZK_ERR_ARG:
+            msg = lib().zk_last_error(ctx._h)
+            raise SetupError(f"zk_groth16_contribute_sound failed ({rc}) {msg.decode() if msg else ''}".strip())
+        _check(rc, ctx, "zk_groth16_contribute_sound")
+        return new
+
+    @staticmethod
+    def verify_contribution(ctx, before, after, coeffs=None):
+        """zk_groth16_verify_contribution_sound: is the CRS `after` a
+        contribution on top of `before`? -> (ok, status), status the first
+        ZK_CONTRIB_* check that fails (SHAPE, FIXED_PART, POINT, DELTA, RATIO)
+        or ZK_CONTRIB_OK.  coeffs: len(h_g1) + len(ic_g1) non-zero integers
+        below 2^128 (h_g1's first); None draws them from `secrets`, which is
+        what a real check uses -- a wrong key then passes with probability
+        about 2^-127.  It does not prove that the contributor knows the share.
+        SetupError for reference-mode keys, ValueError for a bad coefficient."""
+        for crs in (before, after):
+            if not (crs.pk.sound and crs.vk.sound):
+                raise SetupError("verify_contribution: sound keys only")
+        n = len(before.pk.h_g1) + len(before.pk.ic_g1)
+        if coeffs is None:
+            import secrets
+            coeffs = []
+            for _ in range(n):
+                c = 0
+                while not c:      # uniform on [1, 2^128)
+                    c = secrets.randbits(128)
+                coeffs.append(c)
+        co = _fr_rows(coeffs) if len(coeffs) else np.zeros((0, 4), dtype=np.uint64)
+        st = C.c_int(-1)
+        rc = lib().zk_groth16_verify_contribution_sound(
+            C.c_void_p(ctx._h), C.byref(before.pk._bind()), C.byref(before.vk.s), C.byref(after.pk._bind()),
+            C.byref(after.vk.s), _p(co) if len(co) else None, C.c_size_t(len(co)), C.byref(st))
+        _check(rc, ctx, "zk_groth16_verify_contribution_sound")
+        return st.value == ZK_CONTRIB_OK, st.value
 
     @staticmethod
     def generate_device(ctx, qap, params, num_public, shard=0, nshards=1, sound=False, vk=None):

@@ -67,7 +67,7 @@ struct zk_ctx {
   int dist_quotient = -1;                      // -1 distributed when an exchange of the key's shape
                                                // is attached, 0 never (each rank the whole quotient)
   int exchange_first = 0;                      // 1: distributed proofs run the quotient before the MSMs
-  size_t point_chunk = (size_t)1 << 20;        // points per launch of the decompress / validate calls
+  size_t point_chunk = (size_t)1 << 20;        // points per launch of the decompress / validate / g1_mul_scalar calls
   size_t verify_chunk = (size_t)1 << 16;       // proofs / products per launch of the batch verification calls
 
   zk::NttDomain& domain(uint32_t log_n);

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <vector>
 
+#include "ceremony.hpp"
 #include "ctx.hpp"
 #include "pairing.hpp"
 #include "points.hpp"
@@ -98,6 +99,25 @@ int zk_test_fixed_base_g1(zk_ctx* ctx, const zk_fr* scalars, size_t n, zk_g1_aff
 int zk_test_fixed_base_g2(zk_ctx* ctx, const zk_fr* scalars, size_t n, zk_g2_affine* out) {
   if (!ctx || (n && (!scalars || !out))) return ZK_ERR_ARG;
   ZK_TGUARD(ctx, { return fixed_base_wide_host(ctx, true, scalars, n, reinterpret_cast<uint64_t*>(out)); })
+}
+
+// ---- n G1 points times one scalar by the plain 255-bit walk ----------------
+namespace zk {
+__global__ void __launch_bounds__(CM_BLOCK) k_g1_mul_plain(const uint64_t* __restrict__ in, size_t n, CmScalar s,
+                                                           G1X* __restrict__ out) {
+  cm_mul_point<false>(in, n, s, out);
+}
+}  // namespace zk
+int zk_test_g1_mul_scalar_plain(zk_ctx* ctx, const zk_g1_affine* pts, size_t n, const zk_fr* k, zk_g1_affine* out) {
+  if (!ctx || !k || (n && (!pts || !out))) return ZK_ERR_ARG;
+  ZK_TGUARD(ctx, {
+    CmScalar s;
+    if (!cm_plain_scalar(*k, s)) return ZK_ERR_ARG;
+    return g1_mul_scalar_run(ctx, pts, n, out, "g1_mul_scalar_plain",
+                             [&](dim3 grid, hipStream_t st, const uint64_t* d_in, size_t m, G1X* d_x) {
+                               k_g1_mul_plain<<<grid, CM_BLOCK, 0, st>>>(d_in, m, s, d_x);
+                             });
+  })
 }
 
 // ---- the square roots of points.hpp on their own ---------------------------

@@ -183,11 +183,23 @@ int zk_ctx_set_schedule(zk_ctx *ctx, int schedule);
  *                         buffer of zk_groth16_verify_many /
  *                         zk_pairing_products (default 65536: one lane per
  *                         proof, a full wave on every SIMD; >= 1)
+ *   ZK_OPT_GNTT_MAP       lanes of a group transform stage (zk_g1_ntt / zk_g2_ntt):
+ *                         -1 or 1 (default) consecutive lanes take the
+ *                         butterflies of ONE twiddle, so a wave walks one scalar
+ *                         in every stage with 64 or more butterflies per
+ *                         twiddle; 0 consecutive lanes take consecutive
+ *                         twiddles in every stage
+ *   ZK_OPT_SRS_RUN        entries of one column that one lane of the column
+ *                         sums of zk_groth16_setup_srs_sound adds before a second
+ *                         level sums the runs (<= 2^20; 0 the default: the power
+ *                         of two at or above the square root of the longest
+ *                         column, at least 32)
  * (Test hooks -- the virtual-rank prove, the bare exchange, fault injection
  * -- live in a separate library, include/zkp_test.h.) */
 enum { ZK_OPT_QUOTIENT_PATH = 1, ZK_OPT_PROVE_WIN_C = 2, ZK_OPT_EXCHANGE_TIMEOUT_MS = 3,
        ZK_OPT_DIST_QUOTIENT = 5, ZK_OPT_EXCHANGE_FIRST = 6, ZK_OPT_POINT_CHUNK = 7,
-       ZK_OPT_VERIFY_CHUNK = 8, ZK_OPT_SOUND_WIN_C = 9, ZK_OPT_SOUND_COPIES = 10 };
+       ZK_OPT_VERIFY_CHUNK = 8, ZK_OPT_SOUND_WIN_C = 9, ZK_OPT_SOUND_COPIES = 10,
+       ZK_OPT_GNTT_MAP = 12, ZK_OPT_SRS_RUN = 13 };
 int zk_ctx_set_option(zk_ctx *ctx, int option, int64_t value);
 
 /* ---------------------------------------------------------------- MSM --- */
@@ -710,6 +722,86 @@ typedef enum { ZK_CONTRIB_OK = 0, ZK_CONTRIB_SHAPE, ZK_CONTRIB_FIXED_PART,
 int zk_groth16_verify_contribution_sound(zk_ctx *ctx, const zk_pk *before, const zk_vk *vk_before,
                                          const zk_pk *after, const zk_vk *vk_after,
                                          const zk_fr *coeffs, size_t n_coeffs, int *status);
+
+/* ---------------------------------- sound keys from a powers-of-tau string --- */
+/* A contribution (above) removes the trust in delta only: the key it starts
+ * from was made by zk_groth16_setup_sound, whose caller knows tau, alpha and
+ * beta.  The standard remedy (Bowe, Gabizon, Miers: "Scalable multi-party
+ * computation for zk-SNARK parameters in the random beacon model") builds the
+ * initial phase-2 key from a phase-1 STRING of powers instead of from scalars,
+ * with gamma = delta = 1; contributions then randomise delta.  No reference
+ * counterpart.
+ *
+ * The string for domains up to N = 2^log_n; arrays caller-allocated, as zk_pk's:
+ *   tau_g1[i] = [tau^i]_1, i < 2N      tau_g2[i] = [tau^i]_2, i < N
+ *   alpha_tau_g1[i] = [alpha tau^i]_1  beta_tau_g1[i] = [beta tau^i]_1, i < N
+ *   beta_g2 = [beta]_2
+ * OUT OF SCOPE: file formats and the import of foreign transcripts (.ptau). */
+typedef struct {
+  uint32_t log_n;                                   /* N = 2^log_n, the largest domain served */
+  zk_g1_affine *tau_g1;       uint64_t tau_g1_len;  /* 2N: [tau^i]_1                          */
+  zk_g2_affine *tau_g2;       uint64_t tau_g2_len;  /* N                                      */
+  zk_g1_affine *alpha_tau_g1; uint64_t alpha_len;   /* N: [alpha tau^i]_1                     */
+  zk_g1_affine *beta_tau_g1;  uint64_t beta_len;    /* N                                      */
+  zk_g2_affine beta_g2;
+} zk_srs;
+/* A string from KNOWN secrets, for tests, demos and benchmarks: WHOEVER RAN
+ * THIS KNOWS tau, alpha AND beta AND CAN FORGE PROOFS for every key made from
+ * the string, however many contributions follow.  A real string comes out of a
+ * phase-1 ceremony.  The *_len fields of out must hold at least 2N, N, N, N
+ * (else ZK_ERR_ARG) and are set to exactly that.  A zero parameter is
+ * ZK_ERR_SETUP_PARAMS, one >= r ZK_ERR_ARG (as the sound setup), log_n > 31
+ * ZK_ERR_DOMAIN. */
+int zk_srs_generate(zk_ctx *ctx, uint32_t log_n, const zk_fr *tau, const zk_fr *alpha,
+                    const zk_fr *beta, zk_srs *out);
+/* The radix-2 transform of zk_ntt_fr over GROUP elements, in place on a host
+ * array of 2^log_n affine points, natural order in and out: dir = +1 gives
+ * X_k = sum_j w^(jk) P_j, dir = -1 the inverse with 1 / n (anything else
+ * ZK_ERR_ARG); w is zk_ntt_fr's root.  log_n = 0 is the identity map;
+ * log_n > 32 is ZK_ERR_DOMAIN.  The points are ASSUMED valid, as for
+ * zk_g1_mul_scalar; the identity comes out as zero coordinates with infinity
+ * byte 1.  The whole array is resident on the device for a transform (192 B
+ * per G1 and 384 B per G2 point, twice: the passes alternate between two
+ * arrays); the host array crosses PCIe in pieces of ZK_OPT_POINT_CHUNK points. */
+int zk_g1_ntt(zk_ctx *ctx, zk_g1_affine *pts, uint32_t log_n, int dir);
+int zk_g2_ntt(zk_ctx *ctx, zk_g2_affine *pts, uint32_t log_n, int dir);
+/* The sound key of qap from a string, with gamma = delta = 1: entry for entry
+ * and byte for byte what zk_groth16_setup_sound gives for (alpha, beta, 1, 1,
+ * tau), without anyone handing over those scalars.  With n the circuit's domain
+ * (n <= N) and L_i its Lagrange basis, [L_i(tau)]_1 = (1/n) sum_k w^(-ik) [tau^k]_1
+ * is an inverse group transform of the first n powers (three in G1: of tau_g1,
+ * alpha_tau_g1, beta_tau_g1; one in G2), a_g1[j] = sum_i A[i][j] [L_i]_1 a sparse
+ * column sum over points (b_g1, b_g2 likewise), ic[j] = sum_i A[i][j] [beta L_i]_1
+ * + B[i][j] [alpha L_i]_1 + C[i][j] [L_i]_1 (j <= num_public to the vk, the rest
+ * to the pk, both undivided), h_g1[i] = tau_g1[i + n] - tau_g1[i];
+ * alpha_g1 = alpha_tau_g1[0], beta_g1 = beta_tau_g1[0], beta_g2 the string's,
+ * delta_g1, delta_g2, gamma_g2 the generators.  Fills host keys (lengths as
+ * zk_groth16_setup_sound; vk may be NULL); the caller uploads with
+ * zk_pk_upload_sound.  n > N or an array shorter than log_n states ->
+ * ZK_ERR_DOMAIN; num_public >= num_variables -> ZK_ERR_SETUP_PARAMS;
+ * tau_g1[n] == tau_g1[0] (tau on the domain, Z(tau) = 0) ->
+ * ZK_ERR_SETUP_PARAMS with the sound setup's message.  On any error the
+ * outputs are untouched.  The string is ASSUMED valid (zk_srs_verify). */
+int zk_groth16_setup_srs_sound(zk_ctx *ctx, const zk_r1cs_csr *qap, const zk_srs *srs,
+                               uint64_t num_public, zk_pk *pk, zk_vk *vk);
+/* Is srs a well-formed string?  Returns ZK_OK whenever a verdict was reached;
+ * *status is the first check that fails:
+ *   SHAPE      a length is not what log_n states, or n_coeffs != 2N
+ *   POINT      an entry fails zk_g1_validate / zk_g2_validate or is the identity;
+ *              zk_last_error names the array and the index
+ *   GENERATOR  tau_g1[0] or tau_g2[0] is not the generator
+ *   POWERS_G1  e(sum rho_i tau_g1[i+1], g2) e(-sum rho_i tau_g1[i], tau_g2[1]) != 1, i < 2N - 1
+ *   POWERS_G2  e(tau_g1[1], sum rho_i tau_g2[i]) e(-g1, sum rho_i tau_g2[i+1]) != 1, i < N - 1
+ *   ALPHA      e(sum rho_i alpha_tau_g1[i], g2) != e(alpha_tau_g1[0], sum rho_i tau_g2[i]), i < N
+ *   BETA       the same for beta_tau_g1, or e(beta_tau_g1[0], g2) != e(g1, beta_g2)
+ * rho = coeffs as in zk_groth16_verify_contribution_sound: each non-zero and
+ * below 2^128, else ZK_ERR_ARG (after the SHAPE check).  The sums are the public
+ * 255-bit MSMs, the products the host pairing.  OUT OF SCOPE: any contributor's
+ * proof of knowledge -- this establishes that the arrays are consistent powers
+ * of SOME tau, alpha, beta, not where they came from. */
+typedef enum { ZK_SRS_OK = 0, ZK_SRS_SHAPE, ZK_SRS_POINT, ZK_SRS_GENERATOR, ZK_SRS_POWERS_G1,
+               ZK_SRS_POWERS_G2, ZK_SRS_ALPHA, ZK_SRS_BETA } zk_srs_status;
+int zk_srs_verify(zk_ctx *ctx, const zk_srs *srs, const zk_fr *coeffs, size_t n_coeffs, int *status);
 
 #ifdef __cplusplus
 }

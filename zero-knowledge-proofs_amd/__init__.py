@@ -62,6 +62,7 @@ EXPORTS = (
     "zk_proofs_deserialize_compressed", "zk_groth16_verify_many_bytes", "zk_groth16_verify_many_bytes_sound",
     "zk_groth16_verify_all_sound", "zk_groth16_verify_all_bytes_sound",
     "zk_g1_mul_scalar", "zk_groth16_contribute_sound", "zk_groth16_verify_contribution_sound",
+    "zk_srs_generate", "zk_g1_ntt", "zk_g2_ntt", "zk_groth16_setup_srs_sound", "zk_srs_verify",
 )
 # include/zkp_test.h (libzkp_amd_test.so)
 TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fault_after_exchange",
@@ -74,6 +75,8 @@ ZK_OPT_POINT_CHUNK = 7
 ZK_OPT_VERIFY_CHUNK = 8
 ZK_OPT_SOUND_WIN_C = 9
 ZK_OPT_SOUND_COPIES = 10
+ZK_OPT_GNTT_MAP = 12
+ZK_OPT_SRS_RUN = 13
 # zk_verify_status: what a proof / pairing product of a GPU batch call can be
 ZK_VERIFY_REJECT, ZK_VERIFY_ACCEPT, ZK_VERIFY_MALFORMED = range(3)
 # ops of zk_test_fq12 (include/zkp_test.h); FINAL_EXP computes a^(FINAL_EXP_C (p^12 - 1) / r)
@@ -89,6 +92,9 @@ G1_BYTES, G2_BYTES = 48, 96
 # zk_contribution_status: the first check of CRS.verify_contribution that fails
 (ZK_CONTRIB_OK, ZK_CONTRIB_SHAPE, ZK_CONTRIB_FIXED_PART, ZK_CONTRIB_POINT, ZK_CONTRIB_DELTA,
  ZK_CONTRIB_RATIO) = range(6)
+# zk_srs_status: the first check of SRS.verify that fails
+(ZK_SRS_OK, ZK_SRS_SHAPE, ZK_SRS_POINT, ZK_SRS_GENERATOR, ZK_SRS_POWERS_G1, ZK_SRS_POWERS_G2, ZK_SRS_ALPHA,
+ ZK_SRS_BETA) = range(8)
 PROOF_BYTES, PROOF_WORDS = 192, 51
 CSRC = os.path.join(_HERE, "csrc")
 
@@ -189,6 +195,15 @@ class _PK(C.Structure):
 class _VK(C.Structure):
     _fields_ = [("alpha_g1", _G1), ("beta_g2", _G2), ("gamma_g2", _G2), ("delta_g2", _G2),
                 ("ic_g1", C.c_void_p), ("ic_len", C.c_uint64), ("num_public", C.c_uint64)]
+
+
+class _SRS(C.Structure):
+    _fields_ = [("log_n", C.c_uint32),
+                ("tau_g1", C.c_void_p), ("tau_g1_len", C.c_uint64),
+                ("tau_g2", C.c_void_p), ("tau_g2_len", C.c_uint64),
+                ("alpha_tau_g1", C.c_void_p), ("alpha_len", C.c_uint64),
+                ("beta_tau_g1", C.c_void_p), ("beta_len", C.c_uint64),
+                ("beta_g2", _G2)]
 
 
 _lib = None
@@ -794,6 +809,27 @@ class Context:
         _check(rc, self, "zk_ntt_fr")
         return a
 
+    # ---- the same transform over group elements (sound keys from a string) ----
+    def _group_ntt(self, name, points, words, inverse):
+        a = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, words).copy()
+        n = len(a)
+        log_n = n.bit_length() - 1
+        if n == 0 or (1 << log_n) != n:
+            raise DomainTooSmall(f"group NTT size {n} is not a power of two")
+        _check(getattr(lib(), name)(C.c_void_p(self._h), _p(a), C.c_uint32(log_n), C.c_int(-1 if inverse else 1)),
+               self, name)
+        return a
+
+    def g1_ntt(self, points, inverse=False):
+        """zk_g1_ntt: (n, 13) affine words, n a power of two -> (n, 13) words of
+        X_k = sum_j w^(jk) P_j (inverse: w^-1 and 1 / n), natural order in and
+        out, w the root of ntt().  The points are taken as valid."""
+        return self._group_ntt("zk_g1_ntt", points, G1_WORDS, inverse)
+
+    def g2_ntt(self, points, inverse=False):
+        """zk_g2_ntt: g1_ntt over (n, 25) G2 words."""
+        return self._group_ntt("zk_g2_ntt", points, G2_WORDS, inverse)
+
 
 # --------------------------------------------------------------- R1CS ----
 class Variable(int):
@@ -1315,6 +1351,27 @@ class CRS:
     def generate_random(cls, ctx, qap, num_public, rng, sound=False):
         return cls.generate_from_qap(ctx, qap, SetupParams.random(rng), num_public, sound)
 
+    @classmethod
+    def from_srs(cls, ctx, qap, srs, num_public, sound=True):
+        """zk_groth16_setup_srs_sound: the sound CRS of qap from a
+        powers-of-tau string (SRS), with gamma = delta = 1 -- entry for entry
+        generate_from_qap(sound=True) for (alpha, beta, 1, 1, tau), without the
+        scalars: inverse group transforms of the powers give [L_i(tau)], sparse
+        column sums over points the queries.  contribute() then randomises
+        delta.  DomainTooSmall when the circuit's domain exceeds the string's,
+        SetupError for num_public >= num_variables, tau on the domain, or a
+        reference-mode request (truncated scalars: no string can produce them)."""
+        if not sound:
+            raise SetupError("from_srs: sound keys only (a reference-mode key truncates its scalars)")
+        if num_public >= qap.num_variables:
+            raise SetupError("Number of public inputs must be less than total variables")
+        pk = ProvingKey(qap.num_variables, qap.domain_size, num_public, qap, True)
+        vk = VerificationKey(num_public, True)
+        rc = lib().zk_groth16_setup_srs_sound(C.c_void_p(ctx._h), C.byref(qap.csr.s), C.byref(srs._bind()),
+                                              C.c_uint64(num_public), C.byref(pk._bind()), C.byref(vk.s))
+        _check(rc, ctx, "zk_groth16_setup_srs_sound")
+        return cls(pk, vk)
+
     # ---- phase-2 contributions (sound keys) ----
     def copy(self):
         """A CRS with arrays and points of its own."""
@@ -1404,6 +1461,88 @@ class CRS:
                                                   C.c_uint32(shard), C.c_uint32(nshards), C.byref(h))
         _check(rc, ctx, "zk_groth16_setup_dev")
         return DeviceProvingKey(ctx, h.value, qap)
+
+
+class SRS:
+    """A powers-of-tau string (zk_srs) for domains up to N = 2^log_n:
+    tau_g1 (2N, 13), tau_g2 (N, 25), alpha_tau_g1 and beta_tau_g1 (N, 13) words
+    and beta_g2 (25 words).  CRS.from_srs makes a circuit's sound key from it."""
+
+    def __init__(self, log_n):
+        self.log_n = int(log_n)
+        if not 0 <= self.log_n <= 31:
+            raise DomainTooSmall(f"a string for 2^{self.log_n} does not exist (log_n in [0, 31])")
+        N = 1 << self.log_n
+        self.tau_g1 = np.zeros((2 * N, G1_WORDS), dtype=np.uint64)
+        self.tau_g2 = np.zeros((N, G2_WORDS), dtype=np.uint64)
+        self.alpha_tau_g1 = np.zeros((N, G1_WORDS), dtype=np.uint64)
+        self.beta_tau_g1 = np.zeros((N, G1_WORDS), dtype=np.uint64)
+        self.beta_g2 = np.zeros(G2_WORDS, dtype=np.uint64)
+        self.s = _SRS()
+
+    def _bind(self):
+        s = self.s
+        s.log_n = self.log_n
+        for nm, ln in (("tau_g1", "tau_g1_len"), ("tau_g2", "tau_g2_len"), ("alpha_tau_g1", "alpha_len"),
+                       ("beta_tau_g1", "beta_len")):
+            a = getattr(self, nm)
+            if not (isinstance(a, np.ndarray) and a.dtype == np.uint64 and a.flags.c_contiguous):
+                a = np.ascontiguousarray(a, dtype=np.uint64)
+                setattr(self, nm, a)
+            setattr(s, nm, a.ctypes.data)
+            setattr(s, ln, len(a))
+        for i, w in enumerate(np.asarray(self.beta_g2, dtype=np.uint64).reshape(-1)):
+            s.beta_g2.w[i] = int(w)
+        return s
+
+    def copy(self):
+        """A string with arrays of its own."""
+        new = SRS(self.log_n)
+        for nm in ("tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1", "beta_g2"):
+            setattr(new, nm, np.array(getattr(self, nm), dtype=np.uint64, copy=True))
+        return new
+
+    @classmethod
+    def generate(cls, ctx, log_n, tau, alpha, beta):
+        """zk_srs_generate: the string of KNOWN secrets 0 < tau, alpha, beta < r
+        -- for tests, demos and benchmarks: whoever ran this can forge proofs
+        for every key made from the string.  SetupError for a zero or
+        out-of-range parameter."""
+        vals = [int(v) for v in (tau, alpha, beta)]
+        if any(not 0 < v < R for v in vals):
+            raise SetupError("SRS.generate: tau, alpha and beta must be in (0, r)")
+        srs = cls(log_n)
+        s = srs._bind()
+        _check(lib().zk_srs_generate(C.c_void_p(ctx._h), C.c_uint32(srs.log_n), C.byref(_fr(vals[0])),
+                                     C.byref(_fr(vals[1])), C.byref(_fr(vals[2])), C.byref(s)), ctx, "zk_srs_generate")
+        srs.beta_g2 = np.array(s.beta_g2.w, dtype=np.uint64)
+        return srs
+
+    def verify(self, ctx, coeffs=None):
+        """zk_srs_verify: is this a well-formed string? -> (ok, status), status
+        the first ZK_SRS_* check that fails (SHAPE, POINT, GENERATOR, POWERS_G1,
+        POWERS_G2, ALPHA, BETA) or ZK_SRS_OK.  coeffs: 2N non-zero integers below
+        2^128; None draws them from `secrets`, which is what a real check uses.
+        It does not check any contributor's proof of knowledge.  ValueError for
+        a bad coefficient."""
+        N = 1 << self.log_n
+        if coeffs is None:
+            import secrets
+            coeffs = []
+            for _ in range(2 * N):
+                c = 0
+                while not c:      # uniform on [1, 2^128)
+                    c = secrets.randbits(128)
+                coeffs.append(c)
+        coeffs = [int(c) for c in coeffs]
+        if any(not 0 < c < (1 << 128) for c in coeffs):
+            raise ValueError("SRS.verify: every coefficient must be non-zero and below 2^128")
+        co = _fr_rows(coeffs) if len(coeffs) else np.zeros((0, 4), dtype=np.uint64)
+        st = C.c_int(-1)
+        rc = lib().zk_srs_verify(C.c_void_p(ctx._h), C.byref(self._bind()), _p(co) if len(co) else None,
+                                 C.c_size_t(len(co)), C.byref(st))
+        _check(rc, ctx, "zk_srs_verify")
+        return st.value == ZK_SRS_OK, st.value
 
 
 # -------------------------------------------------------------- prove ----

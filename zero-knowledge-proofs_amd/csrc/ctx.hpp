@@ -69,6 +69,8 @@ struct zk_ctx {
   int exchange_first = 0;                      // 1: distributed proofs run the quotient before the MSMs
   size_t point_chunk = (size_t)1 << 20;        // points per launch of the decompress / validate / g1_mul_scalar calls
   size_t verify_chunk = (size_t)1 << 16;       // proofs / products per launch of the batch verification calls
+  int gntt_map = -1;                           // group transform lanes: -1 / 1 twiddle-sharing waves, 0 twiddle per lane
+  uint32_t srs_run = 0;                        // column sums over points: entries per lane, 0 the default (srs.hpp)
 
   zk::NttDomain& domain(uint32_t log_n);
 };

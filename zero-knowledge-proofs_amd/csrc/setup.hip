@@ -337,7 +337,7 @@ static void gen_mul_abi(const HX& G, const zk_fr& k, void* out) {
 static bool fr_canon_zero(const zk_fr& a) { return (a.l[0] | a.l[1] | a.l[2] | a.l[3]) == 0; }
 
 // CSR (rows) -> CSC (columns < V) for one matrix
-static void csr_to_csc(uint64_t nc, uint64_t V, const uint64_t* rp, const uint32_t* col, const zk_fr* val,
+void csr_to_csc(uint64_t nc, uint64_t V, const uint64_t* rp, const uint32_t* col, const zk_fr* val,
                        std::vector<uint64_t>& cp, std::vector<uint32_t>& row, std::vector<zk_fr>& cval) {
   cp.assign(V + 1, 0);
   const uint64_t nnz = nc ? rp[nc] : 0;

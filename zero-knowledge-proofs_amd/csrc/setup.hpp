@@ -13,5 +13,9 @@ int setup_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_setup_params* P, uint
 int fixed_base_wide_host(zk_ctx* ctx, bool g2, const zk_fr* scalars, size_t n, uint64_t* host_out);
 int qap_evaluate_impl(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_fr* point, const zk_fr* z, size_t zlen,
                       zk_fr out[4]);
+// CSR (nc rows) -> CSC over the columns < V: cp[V + 1], the entries' rows and
+// (val != nullptr) their values, column by column in row order
+void csr_to_csc(uint64_t nc, uint64_t V, const uint64_t* rp, const uint32_t* col, const zk_fr* val,
+                std::vector<uint64_t>& cp, std::vector<uint32_t>& row, std::vector<zk_fr>& cval);
 void bases_to_abi_host(bool g2, const void* d_in, uint32_t stride, size_t n, uint64_t* host_out, hipStream_t st);
 }  // namespace zk

@@ -1,0 +1,162 @@
+// srs.hpp -- device helpers of the group transform and the sparse column
+// sums over points (srs.hip): a sound key from a powers-of-tau string.
+//
+// Everything is written once over the field behind the out-of-line products
+// of points.hpp (FqC for G1, Fq2C for G2) and curve.hpp's XYZZ formulas.  A
+// point that a long walk adds again and again stays in memory and is fetched a
+// coordinate at a time where the formula uses it (ceremony.hpp's cm_add_slot,
+// here for both groups): beside the accumulator only the formula's own values
+// are live, which is what lets the G2 walk fit without spills.
+#pragma once
+#include "ceremony.hpp"
+
+namespace zk {
+
+constexpr int GN_BLOCK = 128;
+// Column sums over points: the fewest entries of one column that one lane of
+// the first level adds.  Unless ZK_OPT_SRS_RUN says otherwise the run length is
+// the power of two at or above the square root of the longest column, from
+// here up: a lane of either level then adds about as many points in sequence
+// (DESIGN.md 2.16).
+constexpr uint64_t SRS_RUN_MIN = 32;
+
+template <class F>
+struct GnField;
+template <>
+struct GnField<FqC> {
+  using Raw = Fq;
+  using C = G1;
+  static constexpr int W = 13;
+};
+template <>
+struct GnField<Fq2C> {
+  using Raw = Fq2;
+  using C = G2;
+  static constexpr int W = 25;
+};
+
+ZK_DI FqC gn_ld(const Fq* p) { return {ld_vec(p)}; }
+ZK_DI Fq2C gn_ld(const Fq2* p) { return {ld_vec(p)}; }
+template <class F>
+ZK_DI XYZZ<F> gn_fetch(const XYZZ<typename GnField<F>::Raw>* p) {
+  return {gn_ld(&p->X), gn_ld(&p->Y), gn_ld(&p->ZZ), gn_ld(&p->ZZZ)};
+}
+template <class F>
+ZK_DI void gn_store(XYZZ<typename GnField<F>::Raw>* p, const XYZZ<F>& v) {
+  st_vec(&p->X, v.X.v); st_vec(&p->Y, v.Y.v); st_vec(&p->ZZ, v.ZZ.v); st_vec(&p->ZZZ, v.ZZZ.v);
+}
+// device affine (Montgomery, (0, 0) = infinity); false for the identity
+template <class F>
+ZK_DI bool gn_fetch_aff(const Affine<typename GnField<F>::Raw>* p, Affine<F>& P) {
+  P.x = gn_ld(&p->x);
+  P.y = gn_ld(&p->y);
+  return !aff_is_inf(P);
+}
+// ABI words -> Montgomery affine; false for a set infinity byte (unchecked
+// otherwise, as cm_load)
+ZK_DI bool gn_load_abi(const uint64_t* w, Affine<FqC>& P) { return cm_load(w, P); }
+ZK_DI bool gn_load_abi(const uint64_t* w, Affine<Fq2C>& P) {
+  if (w[24] & 0xff) return false;
+  P.x = {{pt_to_mont(cm_read_fq(w)), pt_to_mont(cm_read_fq(w + 6))}};
+  P.y = {{pt_to_mont(cm_read_fq(w + 12)), pt_to_mont(cm_read_fq(w + 18))}};
+  return true;
+}
+template <class F>
+ZK_DI XYZZ<F> gn_neg(XYZZ<F> p) {
+  p.Y = f_neg(p.Y);
+  return p;
+}
+
+// p + *q by add-2008-s, q's coordinates fetched where the formula uses them
+template <class F>
+ZK_DI XYZZ<F> gn_add_mem(const XYZZ<F>& p, const XYZZ<typename GnField<F>::Raw>* q) {
+  if (f_is_zero(gn_ld(&q->ZZ))) return p;
+  if (xyzz_is_inf(p)) return gn_fetch<F>(q);
+  const F U1 = f_mul(p.X, gn_ld(&q->ZZ));
+  ZK_SB();
+  const F P = f_sub(f_mul(gn_ld(&q->X), p.ZZ), U1);
+  ZK_SB();
+  const F S1 = f_mul(p.Y, gn_ld(&q->ZZZ));
+  ZK_SB();
+  const F R = f_sub(f_mul(gn_ld(&q->Y), p.ZZZ), S1);
+  ZK_SB();
+  if (f_is_zero(P)) {
+    if (f_is_zero(R)) return xyzz_dbl(p);
+    XYZZ<F> r; xyzz_set_inf(r); return r;
+  }
+  XYZZ<F> r;
+  const F PP = f_sqr(P);
+  ZK_SB();
+  r.ZZ = f_mul(p.ZZ, gn_ld(&q->ZZ));
+  ZK_SB();
+  r.ZZ = f_mul(r.ZZ, PP);
+  ZK_SB();
+  const F PPP = f_mul(P, PP);
+  ZK_SB();
+  r.ZZZ = f_mul(p.ZZZ, gn_ld(&q->ZZZ));
+  ZK_SB();
+  r.ZZZ = f_mul(r.ZZZ, PPP);
+  ZK_SB();
+  const F Q = f_mul(U1, PP);
+  ZK_SB();
+  r.X = f_sub(f_sub(f_sqr(R), PPP), f_add(Q, Q));
+  ZK_SB();
+  r.Y = f_mul_sub(R, f_sub(Q, r.X), S1, PPP);
+  ZK_SB();
+  return r;
+}
+
+// The scalar of a walk: four canonical little-endian words and the bits to walk
+struct GnScalar {
+  uint64_t w[4];
+  int top;
+};
+ZK_DI GnScalar gn_scalar(const uint64_t* k) {
+  GnScalar s;
+  s.w[0] = k[0]; s.w[1] = k[1]; s.w[2] = k[2]; s.w[3] = k[3];
+  s.top = s.w[3] ? 256 - __builtin_clzll(s.w[3])
+        : s.w[2] ? 192 - __builtin_clzll(s.w[2])
+        : s.w[1] ? 128 - __builtin_clzll(s.w[1])
+        : s.w[0] ? 64 - __builtin_clzll(s.w[0]) : 0;
+  return s;
+}
+ZK_DI bool gn_bit(const GnScalar& s, int b) {
+  const int j = b >> 6;
+  const uint64_t w = j == 0 ? s.w[0] : j == 1 ? s.w[1] : j == 2 ? s.w[2] : s.w[3];
+  return (w >> (b & 63)) & 1;
+}
+// k * (*base), base an XYZZ value in memory: double-and-add from the top set
+// bit, one doubling per bit and one full addition per set bit
+template <class F>
+ZK_DI XYZZ<F> gn_walk_mem(const XYZZ<typename GnField<F>::Raw>* base, const GnScalar& s) {
+  XYZZ<F> acc;
+  xyzz_set_inf(acc);
+#pragma unroll 1
+  for (int b = s.top - 1; b >= 0; b--) {
+    acc = xyzz_dbl(acc);
+    if (gn_bit(s, b)) acc = gn_add_mem(acc, base);
+  }
+  return acc;
+}
+// k P for an affine P (not the identity): mixed additions
+template <class F>
+ZK_DI XYZZ<F> gn_walk_aff(const Affine<F>& P, const GnScalar& s) {
+  XYZZ<F> acc;
+  xyzz_set_inf(acc);
+#pragma unroll 1
+  for (int b = s.top - 1; b >= 0; b--) {
+    acc = xyzz_dbl(acc);
+    if (gn_bit(s, b)) acc = xyzz_madd(acc, P);
+  }
+  return acc;
+}
+
+// ---- host side (srs.hip) ---------------------------------------------------
+// In-place transform of n = 2^log_n device ABI points (zk_g1_affine /
+// zk_g2_affine words) -> n device affine points (Montgomery) in d_out, on the
+// ctx's main stream; inverse: with 1 / n.  phase: the profiler's name.
+template <class F>
+void gntt_device(zk_ctx* ctx, const uint64_t* d_abi, uint32_t log_n, bool inverse,
+                 Affine<typename GnField<F>::Raw>* d_out, const char* phase);
+
+}  // namespace zk

@@ -803,6 +803,70 @@ typedef enum { ZK_SRS_OK = 0, ZK_SRS_SHAPE, ZK_SRS_POINT, ZK_SRS_GENERATOR, ZK_S
                ZK_SRS_POWERS_G2, ZK_SRS_ALPHA, ZK_SRS_BETA } zk_srs_status;
 int zk_srs_verify(zk_ctx *ctx, const zk_srs *srs, const zk_fr *coeffs, size_t n_coeffs, int *status);
 
+/* ---------------------------------------------- phase-1 contributions --- */
+/* zk_srs_generate's string is known to whoever ran it.  The phase-1 step of a
+ * ceremony removes that: each participant multiplies tau, alpha and beta by
+ * secret shares s, a, b of their own,
+ *   tau_g1[i]       <- s^i   tau_g1[i]        i < 2N
+ *   tau_g2[i]       <- s^i   tau_g2[i]        i < N
+ *   alpha_tau_g1[i] <- a s^i alpha_tau_g1[i]  i < N
+ *   beta_tau_g1[i]  <- b s^i beta_tau_g1[i]   i < N
+ *   beta_g2         <- b     beta_g2
+ * and the string is safe if a single participant forgot their shares.  No
+ * reference counterpart.
+ *
+ * out[i] = k[i] pts[i] for n points and n DIFFERENT scalars, on the GPU, one
+ * lane per point (csrc/mulvec.hpp: per-lane digits select an entry of a small
+ * per-lane table in device memory -- G1 a joint 128-bit walk over P and its
+ * endomorphism image, G2 a joint 64-bit walk over the four images [x^j] P).
+ * The contract of zk_g1_mul_scalar: canonical affine words out; a set infinity
+ * byte or k[i] = 0 gives the identity (zero coordinates, infinity byte 1);
+ * n == 0 -> ZK_OK; out == pts (in place) is allowed; the points are ASSUMED
+ * canonical, on the curve and in the prime-order subgroup; the array crosses
+ * the GPU in chunks of ZK_OPT_POINT_CHUNK points on the ctx's main stream, with
+ * buffers owned by the call (the tables among them: 576 B per G1 and 5760 B per
+ * G2 point of a chunk).  ANY k[i] >= r -> ZK_ERR_ARG before any GPU work;
+ * zk_last_error names the index. */
+int zk_g1_mul_scalars(zk_ctx *ctx, const zk_g1_affine *pts, size_t n, const zk_fr *k /* n */,
+                      zk_g1_affine *out);
+int zk_g2_mul_scalars(zk_ctx *ctx, const zk_g2_affine *pts, size_t n, const zk_fr *k /* n */,
+                      zk_g2_affine *out);
+/* What a contributor publishes beside the new string: [s]_2, [a]_2, [b]_2. */
+typedef struct { zk_g2_affine tau_g2, alpha_g2, beta_g2; } zk_srs_share;
+/* One contribution with the shares s, a, b, in place on a HOST string; share
+ * may be NULL.  A share that is zero or >= r, or an array length that is not
+ * what log_n states -> ZK_ERR_ARG, checked before any GPU work; s = a = b = 1
+ * is legal and leaves the string byte for byte as it was.  The four scalar
+ * arrays are geometric progressions made on the device and never cross PCIe;
+ * beta_g2 and the share points go through the host curve code.  On any error
+ * the string is exactly as it was.  The string is ASSUMED valid
+ * (zk_srs_verify). */
+int zk_srs_contribute(zk_ctx *ctx, zk_srs *srs, const zk_fr *s, const zk_fr *a, const zk_fr *b,
+                      zk_srs_share *share /* may be NULL */);
+/* Is `after` a contribution with the published `share` on top of `before`?
+ * Returns ZK_OK whenever a verdict was reached; *status is the first check
+ * that fails:
+ *   SHAPE   log_n or a length differs between the strings or from what log_n
+ *           states, or n_coeffs != 2N
+ *   SHARE   a share point fails zk_g2_validate or is the identity
+ *   STRING  zk_srs_verify(after, coeffs) gives anything but ZK_SRS_OK; its
+ *           verdict goes to *srs_status (ZK_SRS_OK otherwise)
+ *   TAU     e(after.tau_g1[1], g2) != e(before.tau_g1[1], share.tau_g2)
+ *   ALPHA   the same for alpha_tau_g1[0] and share.alpha_g2
+ *   BETA    the same for beta_tau_g1[0] and share.beta_g2
+ * The new string is consistent powers of some tau', alpha', beta' by STRING;
+ * the three links pin them to s tau, a alpha, b beta for the published shares.
+ * coeffs as zk_srs_verify's (a bad one is ZK_ERR_ARG).  `before` is the
+ * caller's own and is not validated (a malformed point of it fails a link at
+ * best).  OUT OF SCOPE: a proof that the contributor knows s, a, b -- a public
+ * transcript needs one, and it needs a hash to G2; file formats and the import
+ * of foreign transcripts (.ptau). */
+typedef enum { ZK_SRSC_OK = 0, ZK_SRSC_SHAPE, ZK_SRSC_SHARE, ZK_SRSC_STRING,
+               ZK_SRSC_TAU, ZK_SRSC_ALPHA, ZK_SRSC_BETA } zk_srs_contribution_status;
+int zk_srs_verify_contribution(zk_ctx *ctx, const zk_srs *before, const zk_srs *after,
+                               const zk_srs_share *share, const zk_fr *coeffs, size_t n_coeffs,
+                               int *status, int *srs_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,26 @@ int zk_test_fixed_base_g2(zk_ctx *ctx, const zk_fr *scalars, size_t n, zk_g2_aff
  * (profiler phase g1_mul_scalar_plain).  Same arguments, errors and chunking. */
 int zk_test_g1_mul_scalar_plain(zk_ctx *ctx, const zk_g1_affine *pts, size_t n, const zk_fr *k,
                                 zk_g1_affine *out);
+/* zk_g1_mul_scalars / zk_g2_mul_scalars through the plain per-lane 255-bit
+ * double-and-add walk (csrc/srs.hpp, gn_walk_aff, every lane from bit 254)
+ * instead of the table walks of csrc/mulvec.hpp: their on-GPU cross-check and
+ * timing baseline (profiler phases g1_mul_scalars_plain, g2_mul_scalars_plain).
+ * Same arguments, errors and chunking. */
+int zk_test_g1_mul_scalars_plain(zk_ctx *ctx, const zk_g1_affine *pts, size_t n, const zk_fr *k,
+                                 zk_g1_affine *out);
+int zk_test_g2_mul_scalars_plain(zk_ctx *ctx, const zk_g2_affine *pts, size_t n, const zk_fr *k,
+                                 zk_g2_affine *out);
+/* The table walks themselves (profiler phases g1_mul_scalars_table,
+ * g2_mul_scalars_table), whichever walk the public calls ship. */
+int zk_test_g1_mul_scalars_table(zk_ctx *ctx, const zk_g1_affine *pts, size_t n, const zk_fr *k,
+                                 zk_g1_affine *out);
+int zk_test_g2_mul_scalars_table(zk_ctx *ctx, const zk_g2_affine *pts, size_t n, const zk_fr *k,
+                                 zk_g2_affine *out);
+/* The device decomposition of those walks alone, one lane per scalar: for n
+ * canonical scalars below r (else ZK_ERR_ARG), g1_out[4 i ..] = e1 (two words),
+ * e2 (two words) with (e2, e1) = divmod(k[i], x^2), g2_out[4 i ..] = the four
+ * base-x digits of k[i], x = 0xd201000000010000. */
+int zk_test_split_scalars(zk_ctx *ctx, const zk_fr *k, size_t n, uint64_t *g1_out, uint64_t *g2_out);
 /* The device square roots behind point decompression (csrc/points.hpp), one
  * lane per element: in = n canonical Fq (6 words each), out = a canonical
  * root where ok[i] = 1 (zeros where the input has none), largest[i] = the

@@ -63,12 +63,15 @@ EXPORTS = (
     "zk_groth16_verify_all_sound", "zk_groth16_verify_all_bytes_sound",
     "zk_g1_mul_scalar", "zk_groth16_contribute_sound", "zk_groth16_verify_contribution_sound",
     "zk_srs_generate", "zk_g1_ntt", "zk_g2_ntt", "zk_groth16_setup_srs_sound", "zk_srs_verify",
+    "zk_g1_mul_scalars", "zk_g2_mul_scalars", "zk_srs_contribute", "zk_srs_verify_contribution",
 )
 # include/zkp_test.h (libzkp_amd_test.so)
 TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fault_after_exchange",
                 "zk_test_pk_bases", "zk_test_pk_info", "zk_test_pk_plan", "zk_test_fq_sqrt", "zk_test_fq2_sqrt",
                 "zk_test_fq12", "zk_test_pairing_gt", "zk_test_fixed_base_g1", "zk_test_fixed_base_g2",
-                "zk_test_verify_all_parts", "zk_test_g1_mul_scalar_plain")
+                "zk_test_verify_all_parts", "zk_test_g1_mul_scalar_plain",
+                "zk_test_g1_mul_scalars_plain", "zk_test_g2_mul_scalars_plain", "zk_test_g1_mul_scalars_table",
+                "zk_test_g2_mul_scalars_table", "zk_test_split_scalars")
 ZK_OPT_QUOTIENT_PATH, ZK_OPT_PROVE_WIN_C, ZK_OPT_EXCHANGE_TIMEOUT_MS, ZK_OPT_DIST_QUOTIENT = 1, 2, 3, 5
 ZK_OPT_EXCHANGE_FIRST = 6
 ZK_OPT_POINT_CHUNK = 7
@@ -95,6 +98,8 @@ G1_BYTES, G2_BYTES = 48, 96
 # zk_srs_status: the first check of SRS.verify that fails
 (ZK_SRS_OK, ZK_SRS_SHAPE, ZK_SRS_POINT, ZK_SRS_GENERATOR, ZK_SRS_POWERS_G1, ZK_SRS_POWERS_G2, ZK_SRS_ALPHA,
  ZK_SRS_BETA) = range(8)
+# zk_srs_contribution_status: the first check of SRS.verify_contribution that fails
+(ZK_SRSC_OK, ZK_SRSC_SHAPE, ZK_SRSC_SHARE, ZK_SRSC_STRING, ZK_SRSC_TAU, ZK_SRSC_ALPHA, ZK_SRSC_BETA) = range(7)
 PROOF_BYTES, PROOF_WORDS = 192, 51
 CSRC = os.path.join(_HERE, "csrc")
 
@@ -204,6 +209,10 @@ class _SRS(C.Structure):
                 ("alpha_tau_g1", C.c_void_p), ("alpha_len", C.c_uint64),
                 ("beta_tau_g1", C.c_void_p), ("beta_len", C.c_uint64),
                 ("beta_g2", _G2)]
+
+
+class _SRSShare(C.Structure):
+    _fields_ = [("tau_g2", _G2), ("alpha_g2", _G2), ("beta_g2", _G2)]
 
 
 _lib = None
@@ -594,6 +603,73 @@ class Context:
         """zk_test_g1_mul_scalar_plain (test library): g1_mul_scalar through
         the plain 255-bit double-and-add walk."""
         return self._g1_mul_scalar(test_lib().zk_test_g1_mul_scalar_plain, "zk_test_g1_mul_scalar_plain", points, k)
+
+    # ---- n points times n scalars (phase-1 contributions to a string) ----
+    def _mul_scalars(self, load, name, points, scalars, words):
+        a = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, words)
+        ks = [int(k) for k in scalars]
+        if len(ks) != len(a):
+            raise ValueError(f"{name}: {len(a)} points but {len(ks)} scalars")
+        if any(k < 0 or k >> 256 for k in ks):
+            raise ValueError(f"{name}: every scalar must be in [0, r)")
+        # whole values: a scalar >= r is the library's error, which names the index
+        kw = np.array([to_limbs(k) for k in ks], dtype=np.uint64).reshape(-1, 4)
+        out = np.zeros_like(a)
+        fn = getattr(load(), name)
+        _check(fn(C.c_void_p(self._h), _p(a) if len(a) else None, C.c_size_t(len(a)), _p(kw) if len(a) else None,
+                  _p(out) if len(a) else None), self, name)
+        return out
+
+    def g1_mul_scalars(self, points, scalars):
+        """zk_g1_mul_scalars: (n, 13) affine words and n scalars 0 <= k_i < r ->
+        (n, 13) words of k_i * point_i, one lane per point.  The points are
+        taken as canonical, on the curve and in the prime-order subgroup
+        (g1_validate checks that).  ValueError for a scalar >= r (the message
+        names the index)."""
+        return self._mul_scalars(lib, "zk_g1_mul_scalars", points, scalars, G1_WORDS)
+
+    def g2_mul_scalars(self, points, scalars):
+        """zk_g2_mul_scalars: the same for (n, 25) G2 words."""
+        return self._mul_scalars(lib, "zk_g2_mul_scalars", points, scalars, G2_WORDS)
+
+    def test_g1_mul_scalars_plain(self, points, scalars):
+        """zk_test_g1_mul_scalars_plain (test library): g1_mul_scalars through
+        the plain per-lane 255-bit double-and-add walk."""
+        return self._mul_scalars(test_lib, "zk_test_g1_mul_scalars_plain", points,
+                                 scalars, G1_WORDS)
+
+    def test_g2_mul_scalars_plain(self, points, scalars):
+        """zk_test_g2_mul_scalars_plain (test library)."""
+        return self._mul_scalars(test_lib, "zk_test_g2_mul_scalars_plain", points,
+                                 scalars, G2_WORDS)
+
+    def test_g1_mul_scalars_table(self, points, scalars):
+        """zk_test_g1_mul_scalars_table (test library): the table walk,
+        whichever walk g1_mul_scalars ships."""
+        return self._mul_scalars(test_lib, "zk_test_g1_mul_scalars_table", points,
+                                 scalars, G1_WORDS)
+
+    def test_g2_mul_scalars_table(self, points, scalars):
+        """zk_test_g2_mul_scalars_table (test library)."""
+        return self._mul_scalars(test_lib, "zk_test_g2_mul_scalars_table", points,
+                                 scalars, G2_WORDS)
+
+    def test_split_scalars(self, scalars):
+        """zk_test_split_scalars (test library): the device decomposition of n
+        scalars below r -> (g1, g2), two (n, 4) uint64 arrays: e1 (two words)
+        and e2 (two words) with (e2, e1) = divmod(k, x^2), and the four base-x
+        digits of k."""
+        ks = [int(k) for k in scalars]
+        if any(k < 0 or k >> 256 for k in ks):
+            raise ValueError("zk_test_split_scalars: every scalar must be in [0, r)")
+        kw = np.array([to_limbs(k) for k in ks], dtype=np.uint64).reshape(-1, 4)
+        g1 = np.zeros_like(kw)
+        g2 = np.zeros_like(kw)
+        n = len(kw)
+        _check(test_lib().zk_test_split_scalars(C.c_void_p(self._h), _p(kw) if n else None, C.c_size_t(n),
+                                                _p(g1) if n else None, _p(g2) if n else None),
+               self, "zk_test_split_scalars")
+        return g1, g2
 
     # ---- batch verification on the GPU (one lane per proof / product) ----
     @staticmethod
@@ -1543,6 +1619,64 @@ class SRS:
                                  C.c_size_t(len(co)), C.byref(st))
         _check(rc, ctx, "zk_srs_verify")
         return st.value == ZK_SRS_OK, st.value
+
+    def contribute(self, ctx, s, a, b):
+        """zk_srs_contribute: one phase-1 contribution with the secret shares
+        0 < s, a, b < r -> (new_srs, share); this string is left untouched.
+        Entry i of tau_g1 and tau_g2 times s^i, of alpha_tau_g1 times a s^i, of
+        beta_tau_g1 times b s^i (on the GPU), beta_g2 times b: the string
+        generate gives for (tau s, alpha a, beta b).  share: a (3, 25) array,
+        [s]_2, [a]_2, [b]_2, what the contributor publishes for
+        verify_contribution.  ValueError for a zero or out-of-range share,
+        raised before the GPU is touched."""
+        vals = [int(v) for v in (s, a, b)]
+        if any(not 0 < v < R for v in vals):
+            raise ValueError("SRS.contribute: s, a and b must be in (0, r)")
+        new = self.copy()
+        c = new._bind()
+        sh = _SRSShare()
+        _check(lib().zk_srs_contribute(C.c_void_p(ctx._h), C.byref(c), C.byref(_fr(vals[0])), C.byref(_fr(vals[1])),
+                                       C.byref(_fr(vals[2])), C.byref(sh)), ctx, "zk_srs_contribute")
+        new.beta_g2 = np.array(c.beta_g2.w, dtype=np.uint64)
+        share = np.array([list(sh.tau_g2.w), list(sh.alpha_g2.w), list(sh.beta_g2.w)], dtype=np.uint64)
+        return new, share
+
+    @staticmethod
+    def verify_contribution(ctx, before, after, share, coeffs=None):
+        """zk_srs_verify_contribution: is the string `after` a contribution
+        with the published `share` ((3, 25) words: [s]_2, [a]_2, [b]_2) on top of
+        `before`? -> (ok, status, srs_status): status the first ZK_SRSC_* check
+        that fails (SHAPE, SHARE, STRING, TAU, ALPHA, BETA) or ZK_SRSC_OK;
+        srs_status what SRS.verify says of `after` (ZK_SRS_OK unless status is
+        STRING).  coeffs as SRS.verify's (2N of them); None draws them from
+        `secrets`, which is what a real check uses.  It does not prove that the
+        contributor knows the shares.  ValueError for a bad coefficient."""
+        N = 1 << after.log_n
+        if coeffs is None:
+            import secrets
+            coeffs = []
+            for _ in range(2 * N):
+                c = 0
+                while not c:      # uniform on [1, 2^128)
+                    c = secrets.randbits(128)
+                coeffs.append(c)
+        coeffs = [int(c) for c in coeffs]
+        if any(c < 0 or c >> 256 for c in coeffs):
+            raise ValueError("SRS.verify_contribution: every coefficient must be non-zero and below 2^128")
+        # whole values: a bad coefficient is the library's error
+        co = (np.array([to_limbs(c) for c in coeffs], dtype=np.uint64).reshape(-1, 4) if len(coeffs)
+              else np.zeros((0, 4), dtype=np.uint64))
+        shw = np.ascontiguousarray(share, dtype=np.uint64).reshape(3, G2_WORDS)
+        sh = _SRSShare()
+        for f, row in zip((sh.tau_g2, sh.alpha_g2, sh.beta_g2), shw):
+            for i, w in enumerate(row):
+                f.w[i] = int(w)
+        st, sst = C.c_int(-1), C.c_int(-1)
+        rc = lib().zk_srs_verify_contribution(C.c_void_p(ctx._h), C.byref(before._bind()), C.byref(after._bind()),
+                                              C.byref(sh), _p(co) if len(co) else None, C.c_size_t(len(co)),
+                                              C.byref(st), C.byref(sst))
+        _check(rc, ctx, "zk_srs_verify_contribution")
+        return st.value == ZK_SRSC_OK, st.value, sst.value
 
 
 # -------------------------------------------------------------- prove ----

@@ -25,6 +25,7 @@
 #include "host_pairing.hpp"
 #include "prove.hpp"
 #include "setup.hpp"
+#include "mulvec.hpp"
 #include "srs.hpp"
 
 namespace zk {
@@ -258,6 +259,14 @@ struct GnLaunch<Fq2C> {
     k_gn_col_cols_g2<<<ceil_div(V, GN_BLOCK), GN_BLOCK, 0, st>>>(cfr, V, part, out);
   }
 };
+
+template <class F>
+void gn_points_to_abi(const Affine<typename GnField<F>::Raw>* d_in, size_t n, uint64_t* d_out, hipStream_t st) {
+  GnLaunch<F>::to_abi(d_in, n, d_out, st);
+  ZK_LAUNCH_CHECK();
+}
+template void gn_points_to_abi<FqC>(const G1A*, size_t, uint64_t*, hipStream_t);
+template void gn_points_to_abi<Fq2C>(const G2A*, size_t, uint64_t*, hipStream_t);
 
 static Fr fr_words(const uint32_t (&c)[8]) {
   Fr a;
@@ -663,6 +672,97 @@ static int srs_verify(zk_ctx* ctx, const zk_srs* s, const zk_fr* rho, int* statu
   return ZK_OK;
 }
 
+// ------------------------------------------------------- contribution ---
+static bool fr_share_ok(const zk_fr& a) { return !fr_is0(a) && fr_canonical(a); }
+// k P through the host curve code, as canonical ABI words
+static zk_g2_affine host_mul_g2(const host::A2& p, const zk_fr& k) {
+  zk_g2_affine out;
+  std::memset(&out, 0, sizeof out);
+  host_to_abi<G2>(host::mul_scalar(host::from_affine(p.x, p.y, p.inf), k.l), reinterpret_cast<uint64_t*>(&out));
+  return out;
+}
+
+// Entry i of every array times s^i (times a, b for the alpha and beta
+// arrays): the scalars are geometric progressions made on the device
+// (fr_powers) and handed to mulvec.hpp's walks as a device array.
+static int srs_contribute(zk_ctx* ctx, zk_srs* srs, const zk_fr* s, const zk_fr* a, const zk_fr* b,
+                          zk_srs_share* share) {
+  Range range("zk_srs_contribute");
+  hipStream_t st = ctx->stream;
+  const size_t N = (size_t)1 << srs->log_n;
+  host::A2 b2, gen2;
+  zk_g1_affine g1;
+  zk_g2_affine g2;
+  generators(ctx, g1, g2);
+  if (!host::load(srs->beta_g2, b2) || !host::load(g2, gen2)) {
+    ctx->err = "srs_contribute: beta_g2 is not canonical or off its curve";
+    return ZK_ERR_ARG;
+  }
+  // everything into scratch: the string changes only once nothing can fail any more
+  std::vector<zk_g1_affine> t1(2 * N), al(N), be(N);
+  std::vector<zk_g2_affine> t2(N);
+  DevBuf pw;
+  pw.ensure(sizeof(Fr) * 2 * N);
+  const host::Fr sm = host::fr_to_mont(s->l);
+  auto powers = [&](const host::Fr& scale, size_t cnt) {
+    Fr base, sc;
+    const host::Fr bd = host::fr_to_dev(sm), sd = host::fr_to_dev(scale);
+    std::memcpy(base.v, bd.l, 32);
+    std::memcpy(sc.v, sd.l, 32);
+    fr_powers(pw.as<Fr>(), base, sc, cnt, st);
+    fr_from_mont(pw.as<Fr>(), pw.as<uint64_t>(), cnt, st);
+  };
+  powers(host::fr_one(), 2 * N);
+  int rc = mv_mul_scalars<FqC>(ctx, srs->tau_g1, 2 * N, nullptr, pw.as<uint64_t>(), t1.data(), mv_shipped<FqC>(),
+                               "srs_contribute_tau_g1");
+  if (rc == ZK_OK)
+    rc = mv_mul_scalars<Fq2C>(ctx, srs->tau_g2, N, nullptr, pw.as<uint64_t>(), t2.data(), mv_shipped<Fq2C>(),
+                              "srs_contribute_tau_g2");
+  if (rc != ZK_OK) return rc;
+  powers(host::fr_to_mont(a->l), N);
+  rc = mv_mul_scalars<FqC>(ctx, srs->alpha_tau_g1, N, nullptr, pw.as<uint64_t>(), al.data(), mv_shipped<FqC>(),
+                           "srs_contribute_alpha_g1");
+  if (rc != ZK_OK) return rc;
+  powers(host::fr_to_mont(b->l), N);
+  rc = mv_mul_scalars<FqC>(ctx, srs->beta_tau_g1, N, nullptr, pw.as<uint64_t>(), be.data(), mv_shipped<FqC>(),
+                           "srs_contribute_beta_g1");
+  if (rc != ZK_OK) return rc;
+  const zk_g2_affine nb2 = host_mul_g2(b2, *b);
+  if (share) {
+    share->tau_g2 = host_mul_g2(gen2, *s);
+    share->alpha_g2 = host_mul_g2(gen2, *a);
+    share->beta_g2 = host_mul_g2(gen2, *b);
+  }
+  std::memcpy(srs->tau_g1, t1.data(), sizeof(zk_g1_affine) * 2 * N);
+  std::memcpy(srs->tau_g2, t2.data(), sizeof(zk_g2_affine) * N);
+  std::memcpy(srs->alpha_tau_g1, al.data(), sizeof(zk_g1_affine) * N);
+  std::memcpy(srs->beta_tau_g1, be.data(), sizeof(zk_g1_affine) * N);
+  srs->beta_g2 = nb2;
+  return ZK_OK;
+}
+
+static int srs_verify_contribution(zk_ctx* ctx, const zk_srs* before, const zk_srs* after, const zk_srs_share* share,
+                                   const zk_fr* coeffs, size_t n_coeffs, int* status, int* srs_status) {
+  *status = ZK_SRSC_SHARE;
+  const zk_g2_affine sh[3] = {share->tau_g2, share->alpha_g2, share->beta_g2};
+  int rc = ZK_OK;
+  if (!srs_valid(ctx, "share", sh, 3, rc)) return rc;
+  *status = ZK_SRSC_STRING;
+  rc = zk_srs_verify(ctx, after, coeffs, n_coeffs, srs_status);
+  if (rc != ZK_OK || *srs_status != ZK_SRS_OK) return rc;
+  zk_g1_affine g1;
+  zk_g2_affine g2;
+  generators(ctx, g1, g2);
+  *status = ZK_SRSC_TAU;
+  if (!pairs_equal(after->tau_g1[1], g2, before->tau_g1[1], share->tau_g2)) return ZK_OK;
+  *status = ZK_SRSC_ALPHA;
+  if (!pairs_equal(after->alpha_tau_g1[0], g2, before->alpha_tau_g1[0], share->alpha_g2)) return ZK_OK;
+  *status = ZK_SRSC_BETA;
+  if (!pairs_equal(after->beta_tau_g1[0], g2, before->beta_tau_g1[0], share->beta_g2)) return ZK_OK;
+  *status = ZK_SRSC_OK;
+  return ZK_OK;
+}
+
 }  // namespace zk
 
 using namespace zk;
@@ -729,4 +829,39 @@ int zk_srs_verify(zk_ctx* ctx, const zk_srs* srs, const zk_fr* coeffs, size_t n_
       return ZK_ERR_ARG;
     }
   ZK_SGUARD(ctx, { return srs_verify(ctx, srs, coeffs, status); })
+}
+
+// the lengths that log_n states
+static bool srs_shape_ok(const zk_srs* s) {
+  if (s->log_n > 31) return false;
+  const uint64_t N = 1ull << s->log_n;
+  return s->tau_g1_len == 2 * N && s->tau_g2_len == N && s->alpha_len == N && s->beta_len == N;
+}
+
+int zk_srs_contribute(zk_ctx* ctx, zk_srs* srs, const zk_fr* s, const zk_fr* a, const zk_fr* b, zk_srs_share* share) {
+  if (!ctx || !srs || !s || !a || !b) return ZK_ERR_ARG;
+  if (!fr_share_ok(*s) || !fr_share_ok(*a) || !fr_share_ok(*b)) {
+    ctx->err = "srs_contribute: every share must be non-zero and below r";
+    return ZK_ERR_ARG;
+  }
+  if (!srs_shape_ok(srs)) {
+    ctx->err = "srs_contribute: an array's length is not what log_n states";
+    return ZK_ERR_ARG;
+  }
+  if (!srs->tau_g1 || !srs->tau_g2 || !srs->alpha_tau_g1 || !srs->beta_tau_g1) return ZK_ERR_ARG;
+  ZK_SGUARD(ctx, { return srs_contribute(ctx, srs, s, a, b, share); })
+}
+
+int zk_srs_verify_contribution(zk_ctx* ctx, const zk_srs* before, const zk_srs* after, const zk_srs_share* share,
+                               const zk_fr* coeffs, size_t n_coeffs, int* status, int* srs_status) {
+  if (!ctx || !before || !after || !share || !status || !srs_status || (n_coeffs && !coeffs)) return ZK_ERR_ARG;
+  *status = ZK_SRSC_SHAPE;
+  *srs_status = ZK_SRS_OK;
+  if (before->log_n != after->log_n || !srs_shape_ok(before) || !srs_shape_ok(after) ||
+      n_coeffs != 2 * after->tau_g2_len)
+    return ZK_OK;
+  if (!before->tau_g1 || !before->alpha_tau_g1 || !before->beta_tau_g1 || !after->tau_g1 || !after->tau_g2 ||
+      !after->alpha_tau_g1 || !after->beta_tau_g1)
+    return ZK_ERR_ARG;
+  ZK_SGUARD(ctx, { return srs_verify_contribution(ctx, before, after, share, coeffs, n_coeffs, status, srs_status); })
 }

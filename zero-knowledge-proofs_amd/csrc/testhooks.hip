@@ -7,6 +7,7 @@
 
 #include "ceremony.hpp"
 #include "ctx.hpp"
+#include "mulvec.hpp"
 #include "pairing.hpp"
 #include "points.hpp"
 #include "prove.hpp"
@@ -118,6 +119,35 @@ int zk_test_g1_mul_scalar_plain(zk_ctx* ctx, const zk_g1_affine* pts, size_t n, 
                                k_g1_mul_plain<<<grid, CM_BLOCK, 0, st>>>(d_in, m, s, d_x);
                              });
   })
+}
+
+// ---- n points times n scalars: either walk of mulvec.hpp, and its split ----
+namespace zk {
+bool mv_scalars_ok(zk_ctx* ctx, const char* name, const zk_fr* k, size_t n);   // mulvec.hip
+template <class F>
+static int test_mul_scalars(zk_ctx* ctx, const void* pts, size_t n, const zk_fr* k, void* out, MvWalk walk,
+                            const char* phase) {
+  if (!ctx || (n && (!pts || !k || !out))) return ZK_ERR_ARG;
+  if (!mv_scalars_ok(ctx, phase, k, n)) return ZK_ERR_ARG;
+  ZK_TGUARD(ctx, { return mv_mul_scalars<F>(ctx, pts, n, k, nullptr, out, walk, phase); })
+}
+}  // namespace zk
+int zk_test_g1_mul_scalars_plain(zk_ctx* ctx, const zk_g1_affine* pts, size_t n, const zk_fr* k, zk_g1_affine* out) {
+  return test_mul_scalars<FqC>(ctx, pts, n, k, out, MV_PLAIN, "g1_mul_scalars_plain");
+}
+int zk_test_g2_mul_scalars_plain(zk_ctx* ctx, const zk_g2_affine* pts, size_t n, const zk_fr* k, zk_g2_affine* out) {
+  return test_mul_scalars<Fq2C>(ctx, pts, n, k, out, MV_PLAIN, "g2_mul_scalars_plain");
+}
+int zk_test_g1_mul_scalars_table(zk_ctx* ctx, const zk_g1_affine* pts, size_t n, const zk_fr* k, zk_g1_affine* out) {
+  return test_mul_scalars<FqC>(ctx, pts, n, k, out, MV_TABLE, "g1_mul_scalars_table");
+}
+int zk_test_g2_mul_scalars_table(zk_ctx* ctx, const zk_g2_affine* pts, size_t n, const zk_fr* k, zk_g2_affine* out) {
+  return test_mul_scalars<Fq2C>(ctx, pts, n, k, out, MV_TABLE, "g2_mul_scalars_table");
+}
+int zk_test_split_scalars(zk_ctx* ctx, const zk_fr* k, size_t n, uint64_t* g1_out, uint64_t* g2_out) {
+  if (!ctx || (n && !k)) return ZK_ERR_ARG;
+  if (!mv_scalars_ok(ctx, "test_split_scalars", k, n)) return ZK_ERR_ARG;
+  ZK_TGUARD(ctx, { return mv_split_host(ctx, k, n, g1_out, g2_out); })
 }
 
 // ---- the square roots of points.hpp on their own ---------------------------

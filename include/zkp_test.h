@@ -119,6 +119,60 @@ int zk_test_pairing_gt(zk_ctx *ctx, const zk_g1_affine *g1, const zk_g2_affine *
 int zk_test_verify_all_parts(zk_ctx *ctx, const zk_vk *vk, const zk_proof *proofs, const zk_fr *public_inputs,
                              size_t n_inputs, size_t n_proofs, const zk_fr *coeffs, zk_g1_affine *sum_c,
                              zk_fr *scal, uint64_t *gt);
+/* One device field operation of csrc/ff.hpp per element, on operands exactly
+ * as the device holds them: raw 32-bit little-endian limbs in the device's
+ * Montgomery domain (R = 2^392 for Fq, 2^261 for Fr), with no conversion on
+ * the way in or out, so a caller sets every bit.  An element is 8 words (Fr),
+ * 12 (Fq) or 24 (Fq2 and Fq2h: c0 then c1); a, b, c, d and out hold n
+ * elements.  Fq2 runs one lane per element; Fq2h runs the lane-pair form,
+ * element i on lanes 2i (c0) and 2i + 1 (c1).  Every lane of the last wave
+ * stays active (a lane past the end computes on the last element and only its
+ * store is skipped).  b is read by MUL, ADD, SUB, MUL_LAZY and MUL_SUB, c and
+ * d by MUL_SUB only (else they may be NULL).
+ *   Fr, Fq:  MUL SQR ADD SUB NEG DBL INV TO_MONT FROM_MONT
+ *            (INV = fp_inv; TO_MONT = a R, FROM_MONT = a / R)
+ *   Fr only: MUL_LAZY (fp_mul<FrParams, false>: the result is below 2r and
+ *            not reduced further)
+ *   Fq only: MUL_SUB (fq_mul_sub: (a b - c d) / R), FQ_INV (fq_inv)
+ *   Fq2:     MUL SQR INV ADD SUB NEG MUL_SUB
+ *   Fq2h:    MUL SQR MUL_SUB ADD SUB NEG IS_ZERO (out: each lane's verdict,
+ *            0 or 1, as word 0 of its half, the other words 0)
+ * What an operation requires of its operands: ADD, SUB, NEG, DBL, INV and
+ * every Fq2 / Fq2h operation (their products subtract: MUL_SUB, the c0 of a
+ * product) take coefficients below the modulus; the Fr / Fq MUL, SQR,
+ * MUL_LAZY, TO_MONT and FROM_MONT take any words.  Every result but
+ * MUL_LAZY's is below the modulus; INV of 0 is 0.
+ * ZK_ERR_ARG: a null ctx, a needed operand or out missing (n > 0), or a
+ * (field, op) pair not listed.  n = 0 does nothing. */
+enum { ZK_TEST_FIELD_FR = 0, ZK_TEST_FIELD_FQ = 1, ZK_TEST_FIELD_FQ2 = 2, ZK_TEST_FIELD_FQ2H = 3,
+       ZK_TEST_FIELD_FQC = 4, ZK_TEST_FIELD_FQ2C = 5 };
+enum { ZK_TEST_FOP_MUL = 0, ZK_TEST_FOP_SQR = 1, ZK_TEST_FOP_ADD = 2, ZK_TEST_FOP_SUB = 3, ZK_TEST_FOP_NEG = 4,
+       ZK_TEST_FOP_DBL = 5, ZK_TEST_FOP_INV = 6, ZK_TEST_FOP_TO_MONT = 7, ZK_TEST_FOP_FROM_MONT = 8,
+       ZK_TEST_FOP_MUL_LAZY = 9, ZK_TEST_FOP_MUL_SUB = 10, ZK_TEST_FOP_FQ_INV = 11, ZK_TEST_FOP_IS_ZERO = 12 };
+int zk_test_field(zk_ctx *ctx, int field, int op, const uint32_t *a, const uint32_t *b, const uint32_t *c,
+                  const uint32_t *d, size_t n, uint32_t *out);
+/* One point formula of csrc/curve.hpp per element, on the same raw words.  A
+ * coordinate is one field element as above; p and out are XYZZ points (X, Y,
+ * ZZ, ZZZ: 48 words over Fq, 96 over Fq2), q is an XYZZ point for the adds
+ * and an affine point (x, y: 24 / 48 words) for MADD and AFF_DBL.
+ *   DBL xyzz_dbl(p)   DBL_CALL xyzz_dbl_call(p)   AFF_DBL aff_dbl(q)
+ *   MADD xyzz_madd(p, q)   ADD xyzz_add(p, q)   ADD_ILP xyzz_add_ilp(p, q)
+ *   ADD_QUAD xyzz_add_quad(p, q)   ADD_DUO xyzz_add_duo(p, q)
+ * field is FQ, FQ2 (one lane per element), FQ2H (a lane pair per element),
+ * or FQC / FQ2C (the call-based fields of csrc/points.hpp through the same
+ * templates); all take DBL .. ADD_ILP.  ADD_QUAD runs on FQ only and ADD_DUO
+ * on FQ2H only, both with four lanes per element that hold the same p and q;
+ * there out holds every lane's result: 4 n points (ADD_QUAD, one per lane)
+ * or 2 n points (ADD_DUO, one per lane pair), element i first.  Every lane of
+ * the last wave stays active as in zk_test_field.  p is not read by AFF_DBL
+ * and q not by DBL / DBL_CALL (they may be NULL).
+ * Coordinates must be below p; the point at infinity is any point with
+ * ZZ = 0; MADD and AFF_DBL need q not at infinity (AFF_DBL of a point with
+ * y = 0 gives ZZ = 0); nothing is required to lie on the curve.
+ * ZK_ERR_ARG as zk_test_field. */
+enum { ZK_TEST_COP_DBL = 0, ZK_TEST_COP_DBL_CALL = 1, ZK_TEST_COP_AFF_DBL = 2, ZK_TEST_COP_MADD = 3,
+       ZK_TEST_COP_ADD = 4, ZK_TEST_COP_ADD_ILP = 5, ZK_TEST_COP_ADD_QUAD = 6, ZK_TEST_COP_ADD_DUO = 7 };
+int zk_test_curve(zk_ctx *ctx, int field, int op, const uint32_t *p, const uint32_t *q, size_t n, uint32_t *out);
 
 #ifdef __cplusplus
 }

@@ -71,7 +71,7 @@ TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fau
                 "zk_test_fq12", "zk_test_pairing_gt", "zk_test_fixed_base_g1", "zk_test_fixed_base_g2",
                 "zk_test_verify_all_parts", "zk_test_g1_mul_scalar_plain",
                 "zk_test_g1_mul_scalars_plain", "zk_test_g2_mul_scalars_plain", "zk_test_g1_mul_scalars_table",
-                "zk_test_g2_mul_scalars_table", "zk_test_split_scalars")
+                "zk_test_g2_mul_scalars_table", "zk_test_split_scalars", "zk_test_field", "zk_test_curve")
 ZK_OPT_QUOTIENT_PATH, ZK_OPT_PROVE_WIN_C, ZK_OPT_EXCHANGE_TIMEOUT_MS, ZK_OPT_DIST_QUOTIENT = 1, 2, 3, 5
 ZK_OPT_EXCHANGE_FIRST = 6
 ZK_OPT_POINT_CHUNK = 7
@@ -86,6 +86,16 @@ ZK_VERIFY_REJECT, ZK_VERIFY_ACCEPT, ZK_VERIFY_MALFORMED = range(3)
 (ZK_TEST_FQ12_MUL, ZK_TEST_FQ12_SQR, ZK_TEST_FQ12_INV, ZK_TEST_FQ12_CONJ, ZK_TEST_FQ12_FROB1, ZK_TEST_FQ12_FROB2,
  ZK_TEST_FQ12_CYC_SQR, ZK_TEST_FQ12_LINE_MUL, ZK_TEST_FQ12_FINAL_EXP) = range(9)
 FINAL_EXP_C = 3
+# fields and ops of zk_test_field / zk_test_curve (include/zkp_test.h)
+(ZK_TEST_FIELD_FR, ZK_TEST_FIELD_FQ, ZK_TEST_FIELD_FQ2, ZK_TEST_FIELD_FQ2H, ZK_TEST_FIELD_FQC,
+ ZK_TEST_FIELD_FQ2C) = range(6)
+(ZK_TEST_FOP_MUL, ZK_TEST_FOP_SQR, ZK_TEST_FOP_ADD, ZK_TEST_FOP_SUB, ZK_TEST_FOP_NEG, ZK_TEST_FOP_DBL,
+ ZK_TEST_FOP_INV, ZK_TEST_FOP_TO_MONT, ZK_TEST_FOP_FROM_MONT, ZK_TEST_FOP_MUL_LAZY, ZK_TEST_FOP_MUL_SUB,
+ ZK_TEST_FOP_FQ_INV, ZK_TEST_FOP_IS_ZERO) = range(13)
+(ZK_TEST_COP_DBL, ZK_TEST_COP_DBL_CALL, ZK_TEST_COP_AFF_DBL, ZK_TEST_COP_MADD, ZK_TEST_COP_ADD,
+ ZK_TEST_COP_ADD_ILP, ZK_TEST_COP_ADD_QUAD, ZK_TEST_COP_ADD_DUO) = range(8)
+# 32-bit words of one element of each field as those hooks see it
+TEST_FIELD_WORDS = (8, 12, 24, 24, 12, 24)
 FQ12_WORDS = 72
 # zk_point_status: what a decompressed / validated point can be
 ZK_POINT_OK, ZK_POINT_ENCODING, ZK_POINT_NOT_CANONICAL, ZK_POINT_NOT_ON_CURVE, ZK_POINT_NOT_IN_SUBGROUP = range(5)
@@ -871,6 +881,40 @@ class Context:
         _check(test_lib().zk_test_pairing_gt(C.c_void_p(self._h), _p(a), _p(b), C.c_size_t(len(a)), _p(out)), self,
                "zk_test_pairing_gt")
         return out
+
+    # ---- the field and point-formula hooks (include/zkp_test.h) ----
+    def test_field(self, field, op, a, b=None, c=None, d=None):
+        """zk_test_field: (n, W) uint32 raw device words per operand -> (n, W),
+        W = TEST_FIELD_WORDS[field]."""
+        w = TEST_FIELD_WORDS[field]
+        ops = [None if x is None else np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, w) for x in (a, b, c, d)]
+        n = len(ops[0])
+        if any(x is not None and len(x) != n for x in ops):
+            raise ValueError("as many elements in every operand")
+        out = np.zeros((n, w), dtype=np.uint32)
+        args = [_p(x) if x is not None else None for x in ops]
+        _check(test_lib().zk_test_field(C.c_void_p(self._h), C.c_int(int(field)), C.c_int(int(op)), *args,
+                                        C.c_size_t(n), _p(out)), self, "zk_test_field")
+        return out
+
+    def test_curve(self, field, op, p=None, q=None):
+        """zk_test_curve: p (n, 4 W) XYZZ points, q (n, 4 W) XYZZ or (n, 2 W)
+        affine points as raw uint32 device words -> (n, 4 W) points; ADD_QUAD
+        -> (n, 4, 4 W) and ADD_DUO -> (n, 2, 4 W): every lane's / lane pair's
+        result."""
+        w = TEST_FIELD_WORDS[field]
+        aff = op in (ZK_TEST_COP_MADD, ZK_TEST_COP_AFF_DBL)
+        p = None if p is None else np.ascontiguousarray(p, dtype=np.uint32).reshape(-1, 4 * w)
+        q = None if q is None else np.ascontiguousarray(q, dtype=np.uint32).reshape(-1, (2 if aff else 4) * w)
+        n = len(p) if p is not None else len(q)
+        if p is not None and q is not None and len(p) != len(q):
+            raise ValueError("as many q as p")
+        per = {ZK_TEST_COP_ADD_QUAD: 4, ZK_TEST_COP_ADD_DUO: 2}.get(op, 1)
+        out = np.zeros((n, per, 4 * w), dtype=np.uint32)
+        _check(test_lib().zk_test_curve(C.c_void_p(self._h), C.c_int(int(field)), C.c_int(int(op)),
+                                        _p(p) if p is not None else None, _p(q) if q is not None else None,
+                                        C.c_size_t(n), _p(out)), self, "zk_test_curve")
+        return out if per > 1 else out[:, 0]
 
     # ---- NTT (ark-poly Radix2EvaluationDomain fft / ifft / coset) ----
     def ntt(self, data, inverse=False, coset=None):

@@ -250,6 +250,8 @@ ZK_DI Fp<P> fp_mul_limbs(const uint32_t (&x)[P::NL], const uint32_t (&y)[P::NL])
   if constexpr (RED) return fp_reduce_once(o);
   else return o;
 }
+// Contract (tests/test_gpu_field.py): a, b any N words (need not be below m);
+// the result is below m, with RED = false below 2m.
 template <class P, bool RED = true>
 ZK_DI Fp<P> fp_mul(const Fp<P>& a, const Fp<P>& b) {
   uint32_t x[P::NL], y[P::NL];
@@ -259,7 +261,8 @@ ZK_DI Fp<P> fp_mul(const Fp<P>& a, const Fp<P>& b) {
 }
 // Squaring: column k of a^2 is 2 sum_{i<j} a_i a_j (+ a_{k/2}^2), so the
 // product half needs M(M+1)/2 v_mad instead of M^2 (Fq: 105 vs 196); the
-// interleaved Montgomery reduction is unchanged.
+// interleaved Montgomery reduction is unchanged.  Same contract as fp_mul:
+// any N words in, a result below m out.
 template <class P>
 ZK_DI Fp<P> fp_sqr(const Fp<P>& a) {
   constexpr int N = P::N, M = P::NL, LB = P::LB;
@@ -361,6 +364,10 @@ ZK_DI Fq2 fq2_neg(const Fq2& a) { return {fp_neg(a.c0), fp_neg(a.c1)}; }
 // subtracted products go through v_mad_i64_i32 on negated 28-bit limbs; the
 // 4p^2 column offset keeps the total non-negative (a1 b1 < 4 p^2 for inputs
 // < 2p), so signed column sums and arithmetic carries give a value < 2p.
+// Contract: operands below p (the callers' fp_add / fp_sub need that anyway);
+// the result is below p.  With SUB the pre-reduction value is at least
+// 3p^2/R and below p + 5p^2/R, so the final subtraction is taken exactly for
+// results in the lowest ~2^-9 of the field (tests/ff_model.py).
 template <bool SUB>
 ZK_DI Fq fq_redc2(const uint32_t (&x0)[14], const uint32_t (&y0)[14], const uint32_t (&x1)[14],
                   const uint32_t (&y1)[14]) {
@@ -429,6 +436,7 @@ ZK_DI Fq2 fq2_inv(const Fq2& a) {
 
 // a*b - c*d with ONE Montgomery reduction (fq_redc2's signed columns and
 // 4p^2 offset): 588 v_mad instead of 784 for two products and a subtraction.
+// Operands below p; the result is below p.
 ZK_DI Fq fq_mul_sub(const Fq& a, const Fq& b, const Fq& c, const Fq& d) {
   uint32_t xa[14], xb[14], xc[14], xd[14];
   unpack28<12, 14>(a.v, xa);
@@ -461,6 +469,7 @@ ZK_DI void f_set_one(Fq& a) { a = fp_one<FqParams>(); }
 // is then 48 VGPRs per lane instead of 96, so the G2 bucket accumulation fits
 // two waves per SIMD instead of one.  Both lanes of a pair must be active and
 // take the same branches (every predicate below is combined over the pair).
+// Every operation takes coefficients below p and returns them below p.
 struct Fq2h {
   Fq v;
 };
@@ -588,7 +597,7 @@ ZK_DI Fq2h f_sqr(const Fq2h& a) {
 
 // a*b - c*d per lane with ONE reduction: four limb products per column,
 //   lane 0: a0 b0 - a1 b1 - c0 d0 + c1 d1,  lane 1: a1 b0 + a0 b1 - c1 d0 - c0 d1,
-// offset by 4p^2 (the sum is > -2p^2 for inputs < p).
+// offset by 4p^2 (the sum is > -2p^2 for inputs < p, the contract).
 ZK_DI Fq2h f_mul_sub(const Fq2h& a, const Fq2h& b, const Fq2h& c, const Fq2h& d) {
   constexpr int M = 14;
   const bool h = pair_half();

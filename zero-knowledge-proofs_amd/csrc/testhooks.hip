@@ -388,6 +388,302 @@ int zk_test_verify_all_parts(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proof
   })
 }
 
+// ---- one field operation / one point formula of ff.hpp / curve.hpp per element --
+// Raw device words in and out (no Montgomery conversion).  Blocks of one wave;
+// a lane past the last element computes on the last element and skips only its
+// store, so every lane of a pair / quad stays active through the arithmetic
+// (the precondition of the lane-cooperative forms).
+namespace zk {
+constexpr int TF_BLOCK = 64;
+// W: words of one element in memory; LANES: lanes that share it
+template <class F>
+struct TfLay {
+  static constexpr int W = sizeof(F) / 4, LANES = 1;
+};
+template <>
+struct TfLay<Fq2h> {
+  static constexpr int W = 24, LANES = 2;
+};
+template <class F>
+__device__ __forceinline__ F tf_load(const uint32_t* p) {
+  F r;
+  uint32_t* d = reinterpret_cast<uint32_t*>(&r);
+#pragma unroll
+  for (int k = 0; k < (int)(sizeof(F) / 4); k++) d[k] = p[k];
+  return r;
+}
+template <class F>
+__device__ __forceinline__ void tf_store(uint32_t* p, const F& v) {
+  const uint32_t* s = reinterpret_cast<const uint32_t*>(&v);
+#pragma unroll
+  for (int k = 0; k < (int)(sizeof(F) / 4); k++) p[k] = s[k];
+}
+
+template <int OP, class P>
+__device__ __forceinline__ Fp<P> tf_op(const Fp<P>& a, const Fp<P>& b, const Fp<P>& c, const Fp<P>& d) {
+  if constexpr (OP == ZK_TEST_FOP_MUL) return fp_mul(a, b);
+  else if constexpr (OP == ZK_TEST_FOP_SQR) return fp_sqr(a);
+  else if constexpr (OP == ZK_TEST_FOP_ADD) return fp_add(a, b);
+  else if constexpr (OP == ZK_TEST_FOP_SUB) return fp_sub(a, b);
+  else if constexpr (OP == ZK_TEST_FOP_NEG) return fp_neg(a);
+  else if constexpr (OP == ZK_TEST_FOP_DBL) return fp_dbl(a);
+  else if constexpr (OP == ZK_TEST_FOP_INV) return fp_inv(a);
+  else if constexpr (OP == ZK_TEST_FOP_TO_MONT) return fp_to_mont(a);
+  else if constexpr (OP == ZK_TEST_FOP_FROM_MONT) return fp_from_mont(a);
+  else if constexpr (OP == ZK_TEST_FOP_MUL_LAZY) return fp_mul<P, false>(a, b);
+  else if constexpr (OP == ZK_TEST_FOP_MUL_SUB) return fq_mul_sub(a, b, c, d);
+  else return fq_inv(a);
+}
+template <int OP>
+__device__ __forceinline__ Fq2 tf_op(const Fq2& a, const Fq2& b, const Fq2& c, const Fq2& d) {
+  if constexpr (OP == ZK_TEST_FOP_MUL) return fq2_mul(a, b);
+  else if constexpr (OP == ZK_TEST_FOP_SQR) return fq2_sqr(a);
+  else if constexpr (OP == ZK_TEST_FOP_INV) return fq2_inv(a);
+  else if constexpr (OP == ZK_TEST_FOP_ADD) return fq2_add(a, b);
+  else if constexpr (OP == ZK_TEST_FOP_SUB) return fq2_sub(a, b);
+  else if constexpr (OP == ZK_TEST_FOP_NEG) return fq2_neg(a);
+  else return f_mul_sub(a, b, c, d);
+}
+template <int OP>
+__device__ __forceinline__ Fq2h tf_op(const Fq2h& a, const Fq2h& b, const Fq2h& c, const Fq2h& d) {
+  if constexpr (OP == ZK_TEST_FOP_MUL) return f_mul(a, b);
+  else if constexpr (OP == ZK_TEST_FOP_SQR) return f_sqr(a);
+  else if constexpr (OP == ZK_TEST_FOP_MUL_SUB) return f_mul_sub(a, b, c, d);
+  else if constexpr (OP == ZK_TEST_FOP_ADD) return f_add(a, b);
+  else if constexpr (OP == ZK_TEST_FOP_SUB) return f_sub(a, b);
+  else if constexpr (OP == ZK_TEST_FOP_NEG) return f_neg(a);
+  else {
+    Fq2h r;
+    f_set_zero(r);
+    r.v.v[0] = f_is_zero(a) ? 1u : 0u;
+    return r;
+  }
+}
+constexpr bool tf_reads_b(int op) {
+  return op == ZK_TEST_FOP_MUL || op == ZK_TEST_FOP_ADD || op == ZK_TEST_FOP_SUB || op == ZK_TEST_FOP_MUL_LAZY ||
+         op == ZK_TEST_FOP_MUL_SUB;
+}
+
+template <class F, int OP>
+__global__ void __launch_bounds__(TF_BLOCK) k_test_field(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                         const uint32_t* __restrict__ c, const uint32_t* __restrict__ d,
+                                                         size_t n, uint32_t* __restrict__ out) {
+  constexpr int W = TfLay<F>::W, L = TfLay<F>::LANES, S = sizeof(F) / 4;
+  const size_t gid = (size_t)blockIdx.x * TF_BLOCK + threadIdx.x;
+  const size_t e = gid / L, h = gid % L;
+  const bool live = e < n;
+  const size_t off = (live ? e : n - 1) * W + h * S;
+  const F x = tf_load<F>(a + off);
+  F y = x, z = x, w = x;
+  if constexpr (tf_reads_b(OP)) y = tf_load<F>(b + off);
+  if constexpr (OP == ZK_TEST_FOP_MUL_SUB) {
+    z = tf_load<F>(c + off);
+    w = tf_load<F>(d + off);
+  }
+  const F r = tf_op<OP>(x, y, z, w);
+  if (live) tf_store(out + off, r);
+}
+
+template <class F, int OP>
+void tf_launch(zk_ctx* ctx, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, size_t n,
+               uint32_t* out) {
+  const size_t bytes = 4 * (size_t)TfLay<F>::W * n;
+  DevBuf d_in[4], d_out;
+  const uint32_t* h[4] = {a, tf_reads_b(OP) ? b : nullptr, OP == ZK_TEST_FOP_MUL_SUB ? c : nullptr,
+                          OP == ZK_TEST_FOP_MUL_SUB ? d : nullptr};
+  hipStream_t st = ctx->stream;
+  for (int k = 0; k < 4; k++) {
+    if (!h[k]) continue;
+    d_in[k].ensure(bytes);
+    ZK_HIP(hipMemcpyAsync(d_in[k].p, h[k], bytes, hipMemcpyHostToDevice, st));
+  }
+  d_out.ensure(bytes);
+  k_test_field<F, OP><<<ceil_div(n * TfLay<F>::LANES, (size_t)TF_BLOCK), TF_BLOCK, 0, st>>>(
+      d_in[0].as<uint32_t>(), d_in[1].as<uint32_t>(), d_in[2].as<uint32_t>(), d_in[3].as<uint32_t>(), n,
+      d_out.as<uint32_t>());
+  ZK_LAUNCH_CHECK();
+  ZK_HIP(hipMemcpyAsync(out, d_out.p, bytes, hipMemcpyDeviceToHost, st));
+  ZK_HIP(hipStreamSynchronize(st));
+}
+
+// lanes per element of a formula: the field's own, or four for the quad / duo adds
+template <class F, int OP>
+constexpr int tc_lanes() {
+  return (OP == ZK_TEST_COP_ADD_QUAD || OP == ZK_TEST_COP_ADD_DUO) ? 4 : TfLay<F>::LANES;
+}
+template <class F, int OP>
+__global__ void __launch_bounds__(TF_BLOCK) k_test_curve(const uint32_t* __restrict__ p, const uint32_t* __restrict__ q,
+                                                         size_t n, uint32_t* __restrict__ out) {
+  constexpr int W = TfLay<F>::W, L = TfLay<F>::LANES, S = sizeof(F) / 4, LPE = tc_lanes<F, OP>();
+  constexpr bool AFF = OP == ZK_TEST_COP_MADD || OP == ZK_TEST_COP_AFF_DBL;
+  constexpr bool ONE = OP == ZK_TEST_COP_DBL || OP == ZK_TEST_COP_DBL_CALL;
+  const size_t gid = (size_t)blockIdx.x * TF_BLOCK + threadIdx.x;
+  const size_t e = gid / LPE, h = gid % L;
+  const bool live = e < n;
+  const size_t ec = live ? e : n - 1;
+  XYZZ<F> P, Q, r;
+  Affine<F> A;
+  if constexpr (OP != ZK_TEST_COP_AFF_DBL) {
+    const uint32_t* s = p + ec * 4 * W + h * S;
+    P.X = tf_load<F>(s);
+    P.Y = tf_load<F>(s + W);
+    P.ZZ = tf_load<F>(s + 2 * W);
+    P.ZZZ = tf_load<F>(s + 3 * W);
+  }
+  if constexpr (AFF) {
+    const uint32_t* s = q + ec * 2 * W + h * S;
+    A.x = tf_load<F>(s);
+    A.y = tf_load<F>(s + W);
+  } else if constexpr (!ONE) {
+    const uint32_t* s = q + ec * 4 * W + h * S;
+    Q.X = tf_load<F>(s);
+    Q.Y = tf_load<F>(s + W);
+    Q.ZZ = tf_load<F>(s + 2 * W);
+    Q.ZZZ = tf_load<F>(s + 3 * W);
+  }
+  if constexpr (OP == ZK_TEST_COP_DBL) r = xyzz_dbl(P);
+  else if constexpr (OP == ZK_TEST_COP_DBL_CALL) r = xyzz_dbl_call(P);
+  else if constexpr (OP == ZK_TEST_COP_AFF_DBL) r = aff_dbl(A);
+  else if constexpr (OP == ZK_TEST_COP_MADD) r = xyzz_madd(P, A);
+  else if constexpr (OP == ZK_TEST_COP_ADD) r = xyzz_add(P, Q);
+  else if constexpr (OP == ZK_TEST_COP_ADD_ILP) r = xyzz_add_ilp(P, Q);
+  else if constexpr (OP == ZK_TEST_COP_ADD_QUAD) r = xyzz_add_quad(P, Q);
+  else r = xyzz_add_duo(P, Q);
+  if (live) {   // one result per lane (quad), per lane pair (duo), else per element
+    uint32_t* o = out + (gid / L) * 4 * W + h * S;
+    tf_store(o, r.X);
+    tf_store(o + W, r.Y);
+    tf_store(o + 2 * W, r.ZZ);
+    tf_store(o + 3 * W, r.ZZZ);
+  }
+}
+
+template <class F, int OP>
+void tc_launch(zk_ctx* ctx, const uint32_t* p, const uint32_t* q, size_t n, uint32_t* out) {
+  constexpr int W = TfLay<F>::W, L = TfLay<F>::LANES, LPE = tc_lanes<F, OP>();
+  constexpr bool AFF = OP == ZK_TEST_COP_MADD || OP == ZK_TEST_COP_AFF_DBL;
+  const size_t pb = 16 * (size_t)W * n, qb = (AFF ? 8 : 16) * (size_t)W * n, ob = pb * (LPE / L);
+  DevBuf d_p, d_q, d_out;
+  hipStream_t st = ctx->stream;
+  if (p) {
+    d_p.ensure(pb);
+    ZK_HIP(hipMemcpyAsync(d_p.p, p, pb, hipMemcpyHostToDevice, st));
+  }
+  if (q) {
+    d_q.ensure(qb);
+    ZK_HIP(hipMemcpyAsync(d_q.p, q, qb, hipMemcpyHostToDevice, st));
+  }
+  d_out.ensure(ob);
+  k_test_curve<F, OP><<<ceil_div(n * LPE, (size_t)TF_BLOCK), TF_BLOCK, 0, st>>>(d_p.as<uint32_t>(), d_q.as<uint32_t>(), n,
+                                                                               d_out.as<uint32_t>());
+  ZK_LAUNCH_CHECK();
+  ZK_HIP(hipMemcpyAsync(out, d_out.p, ob, hipMemcpyDeviceToHost, st));
+  ZK_HIP(hipStreamSynchronize(st));
+}
+// the six formulas every field takes
+template <class F>
+bool tc_common(zk_ctx* ctx, int op, const uint32_t* p, const uint32_t* q, size_t n, uint32_t* out) {
+  switch (op) {
+    case ZK_TEST_COP_DBL: tc_launch<F, ZK_TEST_COP_DBL>(ctx, p, nullptr, n, out); return true;
+    case ZK_TEST_COP_DBL_CALL: tc_launch<F, ZK_TEST_COP_DBL_CALL>(ctx, p, nullptr, n, out); return true;
+    case ZK_TEST_COP_AFF_DBL: tc_launch<F, ZK_TEST_COP_AFF_DBL>(ctx, nullptr, q, n, out); return true;
+    case ZK_TEST_COP_MADD: tc_launch<F, ZK_TEST_COP_MADD>(ctx, p, q, n, out); return true;
+    case ZK_TEST_COP_ADD: tc_launch<F, ZK_TEST_COP_ADD>(ctx, p, q, n, out); return true;
+    case ZK_TEST_COP_ADD_ILP: tc_launch<F, ZK_TEST_COP_ADD_ILP>(ctx, p, q, n, out); return true;
+    default: return false;
+  }
+}
+}  // namespace zk
+
+#define TF_CASE(F, OP) \
+  case OP: tf_launch<F, OP>(ctx, a, b, c, d, n, out); return ZK_OK;
+int zk_test_field(zk_ctx* ctx, int field, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c,
+                  const uint32_t* d, size_t n, uint32_t* out) {
+  if (!ctx || field < ZK_TEST_FIELD_FR || field > ZK_TEST_FIELD_FQ2H || op < ZK_TEST_FOP_MUL ||
+      op > ZK_TEST_FOP_IS_ZERO)
+    return ZK_ERR_ARG;
+  const bool prime = field == ZK_TEST_FIELD_FR || field == ZK_TEST_FIELD_FQ;
+  bool known;
+  switch (op) {
+    case ZK_TEST_FOP_DBL: case ZK_TEST_FOP_TO_MONT: case ZK_TEST_FOP_FROM_MONT: known = prime; break;
+    case ZK_TEST_FOP_INV: known = field != ZK_TEST_FIELD_FQ2H; break;
+    case ZK_TEST_FOP_MUL_LAZY: known = field == ZK_TEST_FIELD_FR; break;
+    case ZK_TEST_FOP_MUL_SUB: known = field != ZK_TEST_FIELD_FR; break;
+    case ZK_TEST_FOP_FQ_INV: known = field == ZK_TEST_FIELD_FQ; break;
+    case ZK_TEST_FOP_IS_ZERO: known = field == ZK_TEST_FIELD_FQ2H; break;
+    default: known = true; break;
+  }
+  if (!known) return ZK_ERR_ARG;
+  if (n && (!a || !out || (tf_reads_b(op) && !b) || (op == ZK_TEST_FOP_MUL_SUB && (!c || !d)))) return ZK_ERR_ARG;
+  if (!n) return ZK_OK;
+  ZK_TGUARD(ctx, {
+    switch (field) {
+      case ZK_TEST_FIELD_FR:
+        switch (op) {
+          TF_CASE(Fr, ZK_TEST_FOP_MUL) TF_CASE(Fr, ZK_TEST_FOP_SQR) TF_CASE(Fr, ZK_TEST_FOP_ADD)
+          TF_CASE(Fr, ZK_TEST_FOP_SUB) TF_CASE(Fr, ZK_TEST_FOP_NEG) TF_CASE(Fr, ZK_TEST_FOP_DBL)
+          TF_CASE(Fr, ZK_TEST_FOP_INV) TF_CASE(Fr, ZK_TEST_FOP_TO_MONT) TF_CASE(Fr, ZK_TEST_FOP_FROM_MONT)
+          TF_CASE(Fr, ZK_TEST_FOP_MUL_LAZY)
+        }
+        break;
+      case ZK_TEST_FIELD_FQ:
+        switch (op) {
+          TF_CASE(Fq, ZK_TEST_FOP_MUL) TF_CASE(Fq, ZK_TEST_FOP_SQR) TF_CASE(Fq, ZK_TEST_FOP_ADD)
+          TF_CASE(Fq, ZK_TEST_FOP_SUB) TF_CASE(Fq, ZK_TEST_FOP_NEG) TF_CASE(Fq, ZK_TEST_FOP_DBL)
+          TF_CASE(Fq, ZK_TEST_FOP_INV) TF_CASE(Fq, ZK_TEST_FOP_TO_MONT) TF_CASE(Fq, ZK_TEST_FOP_FROM_MONT)
+          TF_CASE(Fq, ZK_TEST_FOP_MUL_SUB) TF_CASE(Fq, ZK_TEST_FOP_FQ_INV)
+        }
+        break;
+      case ZK_TEST_FIELD_FQ2:
+        switch (op) {
+          TF_CASE(Fq2, ZK_TEST_FOP_MUL) TF_CASE(Fq2, ZK_TEST_FOP_SQR) TF_CASE(Fq2, ZK_TEST_FOP_INV)
+          TF_CASE(Fq2, ZK_TEST_FOP_ADD) TF_CASE(Fq2, ZK_TEST_FOP_SUB) TF_CASE(Fq2, ZK_TEST_FOP_NEG)
+          TF_CASE(Fq2, ZK_TEST_FOP_MUL_SUB)
+        }
+        break;
+      default:
+        switch (op) {
+          TF_CASE(Fq2h, ZK_TEST_FOP_MUL) TF_CASE(Fq2h, ZK_TEST_FOP_SQR) TF_CASE(Fq2h, ZK_TEST_FOP_MUL_SUB)
+          TF_CASE(Fq2h, ZK_TEST_FOP_ADD) TF_CASE(Fq2h, ZK_TEST_FOP_SUB) TF_CASE(Fq2h, ZK_TEST_FOP_NEG)
+          TF_CASE(Fq2h, ZK_TEST_FOP_IS_ZERO)
+        }
+        break;
+    }
+    return ZK_ERR_ARG;
+  })
+}
+#undef TF_CASE
+
+int zk_test_curve(zk_ctx* ctx, int field, int op, const uint32_t* p, const uint32_t* q, size_t n, uint32_t* out) {
+  if (!ctx || field < ZK_TEST_FIELD_FQ || field > ZK_TEST_FIELD_FQ2C || op < ZK_TEST_COP_DBL ||
+      op > ZK_TEST_COP_ADD_DUO)
+    return ZK_ERR_ARG;
+  if (op == ZK_TEST_COP_ADD_QUAD && field != ZK_TEST_FIELD_FQ) return ZK_ERR_ARG;
+  if (op == ZK_TEST_COP_ADD_DUO && field != ZK_TEST_FIELD_FQ2H) return ZK_ERR_ARG;
+  const bool reads_p = op != ZK_TEST_COP_AFF_DBL, reads_q = op != ZK_TEST_COP_DBL && op != ZK_TEST_COP_DBL_CALL;
+  if (n && (!out || (reads_p && !p) || (reads_q && !q))) return ZK_ERR_ARG;
+  if (!n) return ZK_OK;
+  ZK_TGUARD(ctx, {
+    bool done;
+    if (op == ZK_TEST_COP_ADD_QUAD) {
+      tc_launch<Fq, ZK_TEST_COP_ADD_QUAD>(ctx, p, q, n, out);
+      done = true;
+    } else if (op == ZK_TEST_COP_ADD_DUO) {
+      tc_launch<Fq2h, ZK_TEST_COP_ADD_DUO>(ctx, p, q, n, out);
+      done = true;
+    } else {
+      switch (field) {
+        case ZK_TEST_FIELD_FQ: done = tc_common<Fq>(ctx, op, p, q, n, out); break;
+        case ZK_TEST_FIELD_FQ2: done = tc_common<Fq2>(ctx, op, p, q, n, out); break;
+        case ZK_TEST_FIELD_FQ2H: done = tc_common<Fq2h>(ctx, op, p, q, n, out); break;
+        case ZK_TEST_FIELD_FQC: done = tc_common<FqC>(ctx, op, p, q, n, out); break;
+        default: done = tc_common<Fq2C>(ctx, op, p, q, n, out); break;
+      }
+    }
+    return done ? ZK_OK : ZK_ERR_ARG;
+  })
+}
+
 int zk_test_pk_info(const zk_pk_dev* pk,uint32_t* win, uint32_t* win_c, uint32_t* shard, uint32_t* nshards) {
   if (!pk || !win || !win_c || !shard || !nshards) return ZK_ERR_ARG;
   *win = (uint32_t)pk->win;

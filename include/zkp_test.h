@@ -84,6 +84,22 @@ int zk_test_g2_mul_scalars_table(zk_ctx *ctx, const zk_g2_affine *pts, size_t n,
  * e2 (two words) with (e2, e1) = divmod(k[i], x^2), g2_out[4 i ..] = the four
  * base-x digits of k[i], x = 0xd201000000010000. */
 int zk_test_split_scalars(zk_ctx *ctx, const zk_fr *k, size_t n, uint64_t *g1_out, uint64_t *g2_out);
+/* The per-lane double-and-add walks of csrc/srs.hpp on their own, one lane per
+ * point in blocks of 128 lanes: out[i] = k[i] pts[i], every lane handing the
+ * helper the top set bit of ITS OWN scalar -- the lengths differ between the
+ * lanes of a wave, exactly as the group transform's stages (gn_stage) and the
+ * column sums (gn_col_runs) call these helpers, and unlike
+ * zk_test_g*_mul_scalars_plain, which walk every lane from bit 254 (the helper
+ * itself walks a wave from its longest lane's top bit).
+ * g2 = 0: pts and out are zk_g1_affine,
+ * 1: zk_g2_affine.  mem = 0: gn_walk_aff (mixed additions of the affine point);
+ * mem = 1: gn_walk_mem, the point stored as XYZZ in a slot of the lane's own
+ * first and fetched a coordinate at a time inside the full addition.  An
+ * identity point or a zero scalar gives the identity; the points are taken as
+ * valid.  A scalar >= r is ZK_ERR_ARG (zk_last_error names the index), as is
+ * g2 or mem outside {0, 1}.  Chunking as zk_g1_mul_scalars
+ * (ZK_OPT_POINT_CHUNK); n = 0 does nothing. */
+int zk_test_gn_walk(zk_ctx *ctx, int g2, int mem, const void *pts, size_t n, const zk_fr *k, void *out);
 /* The device square roots behind point decompression (csrc/points.hpp), one
  * lane per element: in = n canonical Fq (6 words each), out = a canonical
  * root where ok[i] = 1 (zeros where the input has none), largest[i] = the

@@ -11,48 +11,22 @@ import pytest
 
 import points_util as U
 import sound_ref
+import srs_util
+from srs_util import PK_ARRAYS, csr as _csr, same_crs as _same_crs, string as _string, trusted as _trusted
 
 pytestmark = pytest.mark.gpu
 
 R = sound_ref.R
-PK_ARRAYS = ("a_g1", "b_g1", "b_g2", "ic_g1", "h_g1")
-PK_POINTS = ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2")
-VK_POINTS = ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2")
-
-
-def _same_crs(a, b):
-    for nm in PK_ARRAYS:
-        assert np.array_equal(getattr(a.pk, nm), getattr(b.pk, nm)), nm
-    for nm in PK_POINTS:
-        assert np.array_equal(a.pk.point(nm), b.pk.point(nm)), nm
-    assert a.pk.num_public == b.pk.num_public and a.vk.num_public == b.vk.num_public
-    assert np.array_equal(a.vk.ic_g1, b.vk.ic_g1)
-    for nm in VK_POINTS:
-        assert np.array_equal(a.vk.point(nm), b.vk.point(nm)), nm
 
 
 @pytest.fixture(scope="module")
 def case4(pyref):
-    """the parameters, witness and blinding of sound_ref's shared case (n = 4)"""
-    rng = pyref.SplitMix64(sound_ref.CASE_SEED)
-    alpha, beta, _, _, tau = (rng.fr() for _ in range(5))
-    r, s = rng.fr(), rng.fr()
-    return {"alpha": alpha, "beta": beta, "tau": tau, "r": r, "s": s,
-            "z": pyref.synthetic_witness(sound_ref.CASE_N, sound_ref.CASE_SEED + 1)}
+    return srs_util.case4(pyref)
 
 
 @pytest.fixture(scope="module")
 def qap4(zkp):
     return zkp.QAP(zkp.CSRMatrices.synthetic(sound_ref.CASE_N))
-
-
-def _trusted(zkp, ctx, qap, case, num_public):
-    params = zkp.SetupParams(case["alpha"], case["beta"], 1, 1, case["tau"])
-    return zkp.CRS.generate_from_qap(ctx, qap, params, num_public, sound=True)
-
-
-def _string(zkp, ctx, case, log_n):
-    return zkp.SRS.generate(ctx, log_n, case["tau"], case["alpha"], case["beta"])
 
 
 @pytest.fixture(scope="module")

@@ -71,7 +71,8 @@ TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fau
                 "zk_test_fq12", "zk_test_pairing_gt", "zk_test_fixed_base_g1", "zk_test_fixed_base_g2",
                 "zk_test_verify_all_parts", "zk_test_g1_mul_scalar_plain",
                 "zk_test_g1_mul_scalars_plain", "zk_test_g2_mul_scalars_plain", "zk_test_g1_mul_scalars_table",
-                "zk_test_g2_mul_scalars_table", "zk_test_split_scalars", "zk_test_field", "zk_test_curve")
+                "zk_test_g2_mul_scalars_table", "zk_test_split_scalars", "zk_test_field", "zk_test_curve",
+                "zk_test_gn_walk")
 ZK_OPT_QUOTIENT_PATH, ZK_OPT_PROVE_WIN_C, ZK_OPT_EXCHANGE_TIMEOUT_MS, ZK_OPT_DIST_QUOTIENT = 1, 2, 3, 5
 ZK_OPT_EXCHANGE_FIRST = 6
 ZK_OPT_POINT_CHUNK = 7
@@ -663,6 +664,31 @@ class Context:
         """zk_test_g2_mul_scalars_table (test library)."""
         return self._mul_scalars(test_lib, "zk_test_g2_mul_scalars_table", points,
                                  scalars, G2_WORDS)
+
+    def test_gn_walk(self, points, scalars, g2=False, mem=False):
+        """zk_test_gn_walk (test library): (n, 13 | 25) affine words and n
+        scalars 0 <= k_i < r -> the words of k_i * point_i through the per-lane
+        walks of csrc/srs.hpp, every lane from its own top bit: gn_walk_aff
+        (mem=False) or gn_walk_mem (mem=True).  scalars: ints, or an (n, 4)
+        uint64 array of canonical limbs, passed on whole.  ValueError for a
+        scalar >= r (the message names the index)."""
+        words = G2_WORDS if g2 else G1_WORDS
+        a = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, words)
+        if isinstance(scalars, np.ndarray):
+            kw = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        else:
+            ks = [int(k) for k in scalars]
+            if any(k < 0 or k >> 256 for k in ks):
+                raise ValueError("zk_test_gn_walk: every scalar must be in [0, r)")
+            kw = np.array([to_limbs(k) for k in ks], dtype=np.uint64).reshape(-1, 4)
+        n = len(a)
+        if len(kw) != n:
+            raise ValueError(f"zk_test_gn_walk: {n} points but {len(kw)} scalars")
+        out = np.zeros_like(a)
+        _check(test_lib().zk_test_gn_walk(C.c_void_p(self._h), C.c_int(int(bool(g2))), C.c_int(int(bool(mem))),
+                                          _p(a) if n else None, C.c_size_t(n), _p(kw) if n else None,
+                                          _p(out) if n else None), self, "zk_test_gn_walk")
+        return out
 
     def test_split_scalars(self, scalars):
         """zk_test_split_scalars (test library): the device decomposition of n

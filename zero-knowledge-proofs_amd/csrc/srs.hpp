@@ -125,14 +125,32 @@ ZK_DI bool gn_bit(const GnScalar& s, int b) {
   const uint64_t w = j == 0 ? s.w[0] : j == 1 ? s.w[1] : j == 2 ? s.w[2] : s.w[3];
   return (w >> (b & 63)) & 1;
 }
+// The steps of a walk: the largest `top` among the wave's active lanes, found
+// bit by bit through ballots, so the count is one value for the wave and the
+// walk's loop is scalar control flow.  A lane with a shorter scalar doubles the
+// identity through its leading zero bits (gn_bit is 0 there), which costs the
+// wave nothing: it runs its longest lane's steps either way.  A loop whose
+// trip count is a per-lane value went wrong at two waves per SIMD once a launch
+// had more than 256 blocks.
+ZK_DI int gn_wave_top(int top) {
+  int m = 0;
+#pragma unroll
+  for (int bit = 8; bit >= 0; bit--) {
+    const int cand = m | (1 << bit);
+    if (__ballot(top >= cand) != 0) m = cand;
+  }
+  return __builtin_amdgcn_readfirstlane(m);
+}
 // k * (*base), base an XYZZ value in memory: double-and-add from the top set
-// bit, one doubling per bit and one full addition per set bit
+// bit of the wave's longest scalar, one doubling per bit and one full addition
+// per set bit
 template <class F>
 ZK_DI XYZZ<F> gn_walk_mem(const XYZZ<typename GnField<F>::Raw>* base, const GnScalar& s) {
   XYZZ<F> acc;
   xyzz_set_inf(acc);
+  const int steps = gn_wave_top(s.top);
 #pragma unroll 1
-  for (int b = s.top - 1; b >= 0; b--) {
+  for (int b = steps - 1; b >= 0; b--) {
     acc = xyzz_dbl(acc);
     if (gn_bit(s, b)) acc = gn_add_mem(acc, base);
   }
@@ -143,8 +161,9 @@ template <class F>
 ZK_DI XYZZ<F> gn_walk_aff(const Affine<F>& P, const GnScalar& s) {
   XYZZ<F> acc;
   xyzz_set_inf(acc);
+  const int steps = gn_wave_top(s.top);
 #pragma unroll 1
-  for (int b = s.top - 1; b >= 0; b--) {
+  for (int b = steps - 1; b >= 0; b--) {
     acc = xyzz_dbl(acc);
     if (gn_bit(s, b)) acc = xyzz_madd(acc, P);
   }

@@ -2,11 +2,13 @@
 // include/zkp_test.h, built as a separate library on top of libzkp_amd.so so
 // that the shipped ABI (include/zkp.h) holds no way to inject a failure or to
 // drive the virtual-rank path.  Only the GPU tests load it.
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
 #include "ceremony.hpp"
 #include "ctx.hpp"
+#include "msm.hpp"
 #include "mulvec.hpp"
 #include "pairing.hpp"
 #include "points.hpp"
@@ -148,6 +150,101 @@ int zk_test_split_scalars(zk_ctx* ctx, const zk_fr* k, size_t n, uint64_t* g1_ou
   if (!ctx || (n && !k)) return ZK_ERR_ARG;
   if (!mv_scalars_ok(ctx, "test_split_scalars", k, n)) return ZK_ERR_ARG;
   ZK_TGUARD(ctx, { return mv_split_host(ctx, k, n, g1_out, g2_out); })
+}
+
+// ---- the per-lane walks of srs.hpp on their own ----------------------------
+// One lane per point, every lane from its OWN top bit, as gn_stage and
+// gn_col_runs call the helpers (the trip count differs between the lanes of a
+// wave); mv_mul_scalars' chunking.  MEM: the base waits in slot[i] as XYZZ and
+// is fetched a coordinate at a time (gn_walk_mem), else mixed additions
+// (gn_walk_aff).
+namespace zk {
+template <class F, bool MEM>
+ZK_DI void tw_point(const uint64_t* __restrict__ in, size_t n, const uint64_t* __restrict__ k,
+                    XYZZ<typename GnField<F>::Raw>* __restrict__ slot,
+                    XYZZ<typename GnField<F>::Raw>* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * GN_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  Affine<F> P;
+  XYZZ<F> acc;
+  const GnScalar s = gn_scalar(k + 4 * i);
+  if (!gn_load_abi(in + GnField<F>::W * i, P) || s.top == 0) {
+    xyzz_set_inf(acc);
+  } else if constexpr (!MEM) {
+    acc = gn_walk_aff(P, s);
+  } else {
+    gn_store(&slot[i], xyzz_from_aff(P));
+    acc = gn_walk_mem<F>(&slot[i], s);
+  }
+  gn_store(&out[i], acc);
+}
+__global__ void __launch_bounds__(GN_BLOCK) k_test_gn_walk_aff_g1(const uint64_t* __restrict__ in, size_t n,
+                                                                  const uint64_t* __restrict__ k,
+                                                                  G1X* __restrict__ out) {
+  tw_point<FqC, false>(in, n, k, nullptr, out);
+}
+__global__ void __launch_bounds__(GN_BLOCK) k_test_gn_walk_aff_g2(const uint64_t* __restrict__ in, size_t n,
+                                                                  const uint64_t* __restrict__ k,
+                                                                  G2X* __restrict__ out) {
+  tw_point<Fq2C, false>(in, n, k, nullptr, out);
+}
+__global__ void __launch_bounds__(GN_BLOCK) k_test_gn_walk_mem_g1(const uint64_t* __restrict__ in, size_t n,
+                                                                  const uint64_t* __restrict__ k,
+                                                                  G1X* __restrict__ slot, G1X* __restrict__ out) {
+  tw_point<FqC, true>(in, n, k, slot, out);
+}
+__global__ void __launch_bounds__(GN_BLOCK) k_test_gn_walk_mem_g2(const uint64_t* __restrict__ in, size_t n,
+                                                                  const uint64_t* __restrict__ k,
+                                                                  G2X* __restrict__ slot, G2X* __restrict__ out) {
+  tw_point<Fq2C, true>(in, n, k, slot, out);
+}
+static void tw_launch(FqC, bool mem, const uint64_t* in, size_t m, const uint64_t* k, G1X* slot, G1X* out,
+                      hipStream_t st) {
+  if (mem) k_test_gn_walk_mem_g1<<<ceil_div(m, GN_BLOCK), GN_BLOCK, 0, st>>>(in, m, k, slot, out);
+  else k_test_gn_walk_aff_g1<<<ceil_div(m, GN_BLOCK), GN_BLOCK, 0, st>>>(in, m, k, out);
+}
+static void tw_launch(Fq2C, bool mem, const uint64_t* in, size_t m, const uint64_t* k, G2X* slot, G2X* out,
+                      hipStream_t st) {
+  if (mem) k_test_gn_walk_mem_g2<<<ceil_div(m, GN_BLOCK), GN_BLOCK, 0, st>>>(in, m, k, slot, out);
+  else k_test_gn_walk_aff_g2<<<ceil_div(m, GN_BLOCK), GN_BLOCK, 0, st>>>(in, m, k, out);
+}
+
+template <class F>
+static int test_gn_walk(zk_ctx* ctx, bool mem, const void* pts, size_t n, const zk_fr* k, void* out) {
+  using Raw = typename GnField<F>::Raw;
+  using X = XYZZ<Raw>;
+  using A = Affine<Raw>;
+  constexpr size_t SZ = 8 * GnField<F>::W;
+  hipStream_t st = ctx->stream;
+  const size_t chunk = std::min<size_t>(std::max<size_t>(ctx->point_chunk, 1), n);
+  DevBuf d_io, d_k, d_slot, d_x, d_pre, d_aff;
+  d_io.ensure(SZ * chunk);
+  d_k.ensure(sizeof(zk_fr) * chunk);
+  if (mem) d_slot.ensure(sizeof(X) * chunk);
+  d_x.ensure(sizeof(X) * chunk);
+  d_pre.ensure(sizeof(Raw) * chunk);
+  d_aff.ensure(sizeof(A) * chunk);
+  for (size_t lo = 0; lo < n; lo += chunk) {
+    const size_t m = std::min(chunk, n - lo);
+    ZK_HIP(hipMemcpyAsync(d_io.p, static_cast<const char*>(pts) + SZ * lo, SZ * m, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_k.p, k + lo, sizeof(zk_fr) * m, hipMemcpyHostToDevice, st));
+    tw_launch(F{}, mem, d_io.as<uint64_t>(), m, d_k.as<uint64_t>(), d_slot.as<X>(), d_x.as<X>(), st);
+    ZK_LAUNCH_CHECK();
+    batch_normalize<typename GnField<F>::C>(d_x.as<X>(), m, d_pre.as<Raw>(), d_aff.as<A>(), st);
+    gn_points_to_abi<F>(d_aff.as<A>(), m, d_io.as<uint64_t>(), st);
+    ZK_HIP(hipMemcpyAsync(static_cast<char*>(out) + SZ * lo, d_io.p, SZ * m, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));   // the next chunk reuses the buffers
+  }
+  return ZK_OK;
+}
+}  // namespace zk
+int zk_test_gn_walk(zk_ctx* ctx, int g2, int mem, const void* pts, size_t n, const zk_fr* k, void* out) {
+  if (!ctx || (g2 != 0 && g2 != 1) || (mem != 0 && mem != 1) || (n && (!pts || !k || !out))) return ZK_ERR_ARG;
+  if (!mv_scalars_ok(ctx, "test_gn_walk", k, n)) return ZK_ERR_ARG;
+  if (!n) return ZK_OK;
+  ZK_TGUARD(ctx, {
+    return g2 ? test_gn_walk<Fq2C>(ctx, mem != 0, pts, n, k, out) : test_gn_walk<FqC>(ctx, mem != 0, pts, n, k, out);
+  })
 }
 
 // ---- the square roots of points.hpp on their own ---------------------------

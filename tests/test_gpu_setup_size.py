@@ -84,9 +84,9 @@ def test_prove_on_oracle_key_2p20(ctx, zkp, oracle, key_2p20):
     assert np.array_equal(proof.words, oproof)
 
 
-def _ref_rows(opk, slot, idx):
+def _ref_rows(opk, slot, idx, num_public=1):
     if slot == 3:
-        return opk.ic_g1[idx.astype(np.int64) - 2]   # ic_g1[k] <-> variable k + num_public + 1
+        return opk.ic_g1[idx.astype(np.int64) - num_public - 1]   # ic_g1[k] <-> variable k + num_public + 1
     return getattr(opk, dict(SLOTS)[slot])[idx]
 
 

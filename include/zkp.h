@@ -713,10 +713,9 @@ int zk_groth16_contribute_sound(zk_ctx *ctx, zk_pk *pk, zk_vk *vk, const zk_fr *
  * probability about 2^-127 over independent uniform coefficients -- draw them
  * from a cryptographic generator, fresh per call.  The old key is the caller's
  * own and is not validated (a malformed point of it is ZK_ERR_ARG at best).
- * OUT OF SCOPE: a proof that the contributor knows d.  A public transcript
- * needs one for its security proof, and it needs a hash to G2.  What this call
- * establishes is that the new key is a well-formed sound key for some delta'
- * related to the old delta. */
+ * What this call establishes is that the new key is a well-formed sound key
+ * for some delta' related to the old delta; that the contributor KNOWS the
+ * share is what a proof of knowledge (below, role ZK_POK_DELTA) adds. */
 typedef enum { ZK_CONTRIB_OK = 0, ZK_CONTRIB_SHAPE, ZK_CONTRIB_FIXED_PART,
                ZK_CONTRIB_POINT, ZK_CONTRIB_DELTA, ZK_CONTRIB_RATIO } zk_contribution_status;
 int zk_groth16_verify_contribution_sound(zk_ctx *ctx, const zk_pk *before, const zk_vk *vk_before,
@@ -796,9 +795,10 @@ int zk_groth16_setup_srs_sound(zk_ctx *ctx, const zk_r1cs_csr *qap, const zk_srs
  *   BETA       the same for beta_tau_g1, or e(beta_tau_g1[0], g2) != e(g1, beta_g2)
  * rho = coeffs as in zk_groth16_verify_contribution_sound: each non-zero and
  * below 2^128, else ZK_ERR_ARG (after the SHAPE check).  The sums are the public
- * 255-bit MSMs, the products the host pairing.  OUT OF SCOPE: any contributor's
- * proof of knowledge -- this establishes that the arrays are consistent powers
- * of SOME tau, alpha, beta, not where they came from. */
+ * 255-bit MSMs, the products the host pairing.  This establishes that the
+ * arrays are consistent powers of SOME tau, alpha, beta, not where they came
+ * from: the contributors' proofs of knowledge are checked by
+ * zk_srs_verify_contribution_proofs (below). */
 typedef enum { ZK_SRS_OK = 0, ZK_SRS_SHAPE, ZK_SRS_POINT, ZK_SRS_GENERATOR, ZK_SRS_POWERS_G1,
                ZK_SRS_POWERS_G2, ZK_SRS_ALPHA, ZK_SRS_BETA } zk_srs_status;
 int zk_srs_verify(zk_ctx *ctx, const zk_srs *srs, const zk_fr *coeffs, size_t n_coeffs, int *status);
@@ -858,14 +858,116 @@ int zk_srs_contribute(zk_ctx *ctx, zk_srs *srs, const zk_fr *s, const zk_fr *a, 
  * the three links pin them to s tau, a alpha, b beta for the published shares.
  * coeffs as zk_srs_verify's (a bad one is ZK_ERR_ARG).  `before` is the
  * caller's own and is not validated (a malformed point of it fails a link at
- * best).  OUT OF SCOPE: a proof that the contributor knows s, a, b -- a public
- * transcript needs one, and it needs a hash to G2; file formats and the import
- * of foreign transcripts (.ptau). */
+ * best).  That the contributor knows s, a, b is a separate check:
+ * zk_srs_verify_contribution_proofs (below); a full audit runs both.  OUT OF
+ * SCOPE: file formats and the import of foreign transcripts (.ptau). */
 typedef enum { ZK_SRSC_OK = 0, ZK_SRSC_SHAPE, ZK_SRSC_SHARE, ZK_SRSC_STRING,
                ZK_SRSC_TAU, ZK_SRSC_ALPHA, ZK_SRSC_BETA } zk_srs_contribution_status;
 int zk_srs_verify_contribution(zk_ctx *ctx, const zk_srs *before, const zk_srs *after,
                                const zk_srs_share *share, const zk_fr *coeffs, size_t n_coeffs,
                                int *status, int *srs_status);
+
+/* ------------------------------------------------- proofs of knowledge --- */
+/* The checks above establish that a new string or key is consistent for SOME
+ * shares.  The security argument of Bowe, Gabizon, Miers needs each
+ * contributor to prove KNOWLEDGE of their share, bound to the state they
+ * started from: with R a point of G2 hashed from that state and from [s]_1,
+ * the pair ([s]_1, [s] R) can only be made by someone who knows s.  No
+ * reference counterpart.
+ *
+ * The hash to G2, ZKAMD-H2G2-V1 (this project's own construction, try and
+ * increment -- NOT RFC 9380, whose SSWU map and isogeny are OUT OF SCOPE; the
+ * inputs are public, so nothing here is constant-time).  With len(dst) <= 255:
+ *   m0 = SHA-256("ZKAMD-H2G2-V1" | byte(len(dst)) | dst | msg)
+ *   for ctr = 0 .. 255:
+ *     d_j = SHA-256(m0 | byte(ctr) | byte(j)), j = 0..4
+ *     x   = (int_be(d_0 | d_1) mod p) + (int_be(d_2 | d_3) mod p) u
+ *     t   = x^3 + 4 (1 + u);  t == 0 or t not a square in Fq2 -> next ctr
+ *     y   = the root of t whose sort flag (that of the compressed encoding:
+ *           c1, or c0 when c1 == 0, above (p - 1) / 2) equals d_4[31] & 1
+ *     Q   = [x^2 - x - 1] P + [x - 1] psi(P) + psi^2([2] P), P = (x, y),
+ *           x = -0xd201000000010000 (Budroni-Pintore cofactor clearing,
+ *           = [h_eff] P);  Q != O -> the hash is Q, tries = ctr
+ *   no point after 256 tries -> an error (probability about 2^-256)
+ *
+ * SHA-256 of len bytes.  Host only. */
+int zk_sha256(const uint8_t *msg, size_t len, uint8_t out[32]);
+/* One hash on the host.  dst_len > 255 -> ZK_ERR_ARG; no point after 256
+ * tries -> ZK_ERR_ARG with *tries = 0xff and out zeroed.  tries may be NULL. */
+int zk_hash_to_g2_host(const uint8_t *msg, size_t msg_len, const uint8_t *dst, size_t dst_len,
+                       zk_g2_affine *out, uint8_t *tries /* may be NULL */);
+/* n hashes on the GPU, one lane per message (csrc/hash.hpp): msgs is n x
+ * msg_len bytes, message i at msgs + i msg_len (no alignment assumed), all
+ * with the one dst.  out[i]: canonical affine words; tries[i] (may be NULL):
+ * the counter that gave the point, or 0xff with out[i] all zero where there
+ * was none.  dst_len > 255 -> ZK_ERR_ARG; n == 0 -> ZK_OK.  The batch crosses
+ * the GPU in chunks of ZK_OPT_POINT_CHUNK messages. */
+int zk_hash_to_g2(zk_ctx *ctx, const uint8_t *msgs, size_t n, size_t msg_len,
+                  const uint8_t *dst, size_t dst_len, zk_g2_affine *out, uint8_t *tries /* may be NULL */);
+
+/* A proof of knowledge of s: [s]_1 and [s] R with
+ *   R = H2G2(challenge | compress(s_g1) | byte(role), "ZKAMD-POK-V1")
+ * (an 81-byte message; compress = zk_g1_compress's 48 bytes).  The role keeps
+ * the proofs of one contribution apart; the challenge binds a proof to the
+ * state the contribution started from (zk_srs_digest / zk_groth16_key_digest_sound). */
+typedef struct { zk_g1_affine s_g1; zk_g2_affine s_r; } zk_pok;     /* [s]_1 and [s] R */
+enum { ZK_POK_TAU = 0, ZK_POK_ALPHA = 1, ZK_POK_BETA = 2, ZK_POK_DELTA = 3 };   /* role */
+/* What a proof can be: the first check that fails.
+ *   POINT   s_g1 fails zk_g1_validate or s_r fails zk_g2_validate, or either is
+ *           the identity
+ *   REJECT  e(s_g1, R) e(-g1, s_r) != 1 (zk_srs_verify_contribution_proofs:
+ *           or the link to the published share fails)
+ *   HASH    no R after 256 tries */
+typedef enum { ZK_POK_OK = 0, ZK_POK_POINT, ZK_POK_REJECT, ZK_POK_HASH } zk_pok_status;
+/* Host only.  s = 0, s >= r or role > 3 -> ZK_ERR_ARG. */
+int zk_pok_make(const zk_fr *s, uint8_t role, const uint8_t challenge[32], zk_pok *out);          /* host */
+/* Host only: one proof through the host hash and the host pairing.  ZK_OK
+ * whenever a verdict was reached; role > 3 -> ZK_ERR_ARG. */
+int zk_pok_verify(const zk_pok *pok, uint8_t role, const uint8_t challenge[32], int *status);     /* host */
+/* n proofs on the GPU, status[i] (a zk_pok_status) what zk_pok_verify gives
+ * for proof i alone: point validation, the hash and the two-pair product all
+ * run on the device in one call and R never visits the host (the arrangement
+ * of zk_groth16_verify_many_bytes).  challenges is n x 32 bytes.  *first_bad
+ * (may be NULL): the lowest index whose status is not OK, or n.  ZK_OK
+ * whenever every proof got a status; a role > 3 -> ZK_ERR_ARG before any GPU
+ * work (zk_last_error names the index); n == 0 -> ZK_OK.  The batch crosses
+ * the GPU in chunks of ZK_OPT_VERIFY_CHUNK proofs. */
+int zk_pok_verify_many(zk_ctx *ctx, const zk_pok *poks, const uint8_t *roles, const uint8_t *challenges /* n x 32 */,
+                       size_t n, uint8_t *status, size_t *first_bad /* may be NULL */);
+/* The challenge of a phase-1 contribution: SHA-256 over
+ *   "ZKAMD-SRS-V1" (12 bytes) | be64(log_n) | be64(tau_g1_len) | be64(tau_g2_len)
+ *   | be64(alpha_len) | be64(beta_len)
+ *   | compress(tau_g1[0..]) | compress(tau_g2[0..]) | compress(alpha_tau_g1[0..])
+ *   | compress(beta_tau_g1[0..]) | compress(beta_g2)
+ * with be64 a big-endian u64 and compress the 48 / 96 bytes of zk_g1_compress /
+ * zk_g2_compress per point.  Host only; the encoding is streamed through the
+ * hash, never held whole. */
+int zk_srs_digest(const zk_srs *srs, uint8_t out[32]);                                             /* host */
+/* The challenge of a phase-2 contribution: SHA-256 over
+ *   "ZKAMD-KEY-V1" (12 bytes) | be64(a_len) | be64(b_len) | be64(b2_len) | be64(ic_len)
+ *   | be64(h_len) | be64(num_public) | be64(vk ic_len)
+ *   | compress of the pk in zk_pk order: alpha_g1, beta_g1, delta_g1, beta_g2,
+ *     delta_g2, a_g1[0..], b_g1[0..], b_g2[0..], ic_g1[0..], h_g1[0..]
+ *   | compress(vk gamma_g2) | compress(vk ic_g1[0..])
+ * (the vk's alpha_g1, beta_g2 and delta_g2 are the pk's).  Host only. */
+int zk_groth16_key_digest_sound(const zk_pk *pk, const zk_vk *vk, uint8_t out[32]);                /* host */
+
+/* Phase 1: the three proofs of one zk_srs_contribute(before, s, a, b), roles
+ * TAU, ALPHA, BETA, challenge zk_srs_digest(before).  Host only; the shares as
+ * zk_srs_contribute takes them (zero or >= r -> ZK_ERR_ARG). */
+typedef struct { zk_pok tau, alpha, beta; } zk_srs_contribution_proof;
+int zk_srs_prove_contribution(const zk_srs *before, const zk_fr *s, const zk_fr *a, const zk_fr *b,
+                              zk_srs_contribution_proof *out);                                     /* host */
+/* The transcript check for m contributions: zk_pok_verify_many over the 3 m
+ * proofs (status[3 i + j] for proof tau, alpha, beta of contribution i,
+ * challenge before_digests + 32 i), and per proof the link to the published
+ * share, e(s_g1, g2) e(-g1, share point) = 1, as a second two-pair product in
+ * the same device pass; a failed link is REJECT.  The share points themselves
+ * are validated by zk_srs_verify_contribution, which this call does not
+ * replace: a full audit runs both.  ZK_OK whenever every proof got a status. */
+int zk_srs_verify_contribution_proofs(zk_ctx *ctx, const uint8_t *before_digests /* m x 32 */,
+                                      const zk_srs_share *shares, const zk_srs_contribution_proof *proofs,
+                                      size_t m, uint8_t *status /* 3m */);
 
 #ifdef __cplusplus
 }

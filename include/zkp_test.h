@@ -189,6 +189,12 @@ int zk_test_field(zk_ctx *ctx, int field, int op, const uint32_t *a, const uint3
 enum { ZK_TEST_COP_DBL = 0, ZK_TEST_COP_DBL_CALL = 1, ZK_TEST_COP_AFF_DBL = 2, ZK_TEST_COP_MADD = 3,
        ZK_TEST_COP_ADD = 4, ZK_TEST_COP_ADD_ILP = 5, ZK_TEST_COP_ADD_QUAD = 6, ZK_TEST_COP_ADD_DUO = 7 };
 int zk_test_curve(zk_ctx *ctx, int field, int op, const uint32_t *p, const uint32_t *q, size_t n, uint32_t *out);
+/* zk_hash_to_g2 through the same kernel with a cap on the tries: a message
+ * that needs more than max_tries (1 .. 256, else ZK_ERR_ARG) comes back as
+ * tries = 0xff with zero words.  Shows the loop leaving at the cap and the
+ * lanes that found a point earlier keeping it. */
+int zk_test_hash_to_g2_capped(zk_ctx *ctx, const uint8_t *msgs, size_t n, size_t msg_len, const uint8_t *dst,
+                              size_t dst_len, uint32_t max_tries, zk_g2_affine *out, uint8_t *tries);
 
 #ifdef __cplusplus
 }

@@ -64,6 +64,9 @@ EXPORTS = (
     "zk_g1_mul_scalar", "zk_groth16_contribute_sound", "zk_groth16_verify_contribution_sound",
     "zk_srs_generate", "zk_g1_ntt", "zk_g2_ntt", "zk_groth16_setup_srs_sound", "zk_srs_verify",
     "zk_g1_mul_scalars", "zk_g2_mul_scalars", "zk_srs_contribute", "zk_srs_verify_contribution",
+    "zk_sha256", "zk_hash_to_g2_host", "zk_hash_to_g2", "zk_pok_make", "zk_pok_verify", "zk_pok_verify_many",
+    "zk_srs_digest", "zk_groth16_key_digest_sound", "zk_srs_prove_contribution",
+    "zk_srs_verify_contribution_proofs",
 )
 # include/zkp_test.h (libzkp_amd_test.so)
 TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fault_after_exchange",
@@ -72,7 +75,7 @@ TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fau
                 "zk_test_verify_all_parts", "zk_test_g1_mul_scalar_plain",
                 "zk_test_g1_mul_scalars_plain", "zk_test_g2_mul_scalars_plain", "zk_test_g1_mul_scalars_table",
                 "zk_test_g2_mul_scalars_table", "zk_test_split_scalars", "zk_test_field", "zk_test_curve",
-                "zk_test_gn_walk")
+                "zk_test_gn_walk", "zk_test_hash_to_g2_capped")
 ZK_OPT_QUOTIENT_PATH, ZK_OPT_PROVE_WIN_C, ZK_OPT_EXCHANGE_TIMEOUT_MS, ZK_OPT_DIST_QUOTIENT = 1, 2, 3, 5
 ZK_OPT_EXCHANGE_FIRST = 6
 ZK_OPT_POINT_CHUNK = 7
@@ -112,6 +115,16 @@ G1_BYTES, G2_BYTES = 48, 96
 # zk_srs_contribution_status: the first check of SRS.verify_contribution that fails
 (ZK_SRSC_OK, ZK_SRSC_SHAPE, ZK_SRSC_SHARE, ZK_SRSC_STRING, ZK_SRSC_TAU, ZK_SRSC_ALPHA, ZK_SRSC_BETA) = range(7)
 PROOF_BYTES, PROOF_WORDS = 192, 51
+# proofs of knowledge (zk_pok): the role of a proof, and zk_pok_status
+ZK_POK_TAU, ZK_POK_ALPHA, ZK_POK_BETA, ZK_POK_DELTA = range(4)
+ZK_POK_OK, ZK_POK_POINT, ZK_POK_REJECT, ZK_POK_HASH = range(4)
+POK_WORDS = G1_WORDS + G2_WORDS     # a zk_pok: s_g1 then s_r
+H2_NO_POINT = 0xFF                  # the tries byte of a message the hash found no point for
+POK_DST = b"ZKAMD-POK-V1"
+FQ_MODULUS = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
+G1_GENERATOR = (
+    0x17F1D3A73197D7942695638C4FA9AC0FC3688C4F9774B905A14E3A3F171BAC586C55E83FF97A1AEFFB3AF00ADB22C6BB,
+    0x08B3F481E3AAA0F1A09E30ED741D8AE4FCF5E095D5D00AF600DB18CB2C04B3EDD03CC744A2888AE40CAA232946C5E7E1)
 CSRC = os.path.join(_HERE, "csrc")
 
 
@@ -224,6 +237,14 @@ class _SRS(C.Structure):
 
 class _SRSShare(C.Structure):
     _fields_ = [("tau_g2", _G2), ("alpha_g2", _G2), ("beta_g2", _G2)]
+
+
+class _Pok(C.Structure):
+    _fields_ = [("s_g1", _G1), ("s_r", _G2)]
+
+
+class _SRSProof(C.Structure):
+    _fields_ = [("tau", _Pok), ("alpha", _Pok), ("beta", _Pok)]
 
 
 _lib = None
@@ -884,6 +905,64 @@ class Context:
         _check(rc, self, "zk_pairing_products")
         return st
 
+    # ---- the hash to G2 and proofs of knowledge (include/zkp.h) ----
+    @staticmethod
+    def _messages(msgs):
+        if isinstance(msgs, np.ndarray):
+            m = np.ascontiguousarray(msgs, dtype=np.uint8)
+            if m.ndim != 2:
+                raise ValueError("hash_to_g2: messages as an (n, msg_len) uint8 array")
+            return m
+        msgs = [bytes(x) for x in msgs]
+        if len({len(x) for x in msgs}) > 1:
+            raise ValueError("hash_to_g2: the messages of one call share their length")
+        ln = len(msgs[0]) if msgs else 0
+        return np.frombuffer(b"".join(msgs), dtype=np.uint8).reshape(len(msgs), ln).copy()
+
+    def _hash_to_g2(self, fn, name, msgs, dst, *extra):
+        m = self._messages(msgs)
+        n, ln = m.shape
+        dst = bytes(dst)
+        out = np.zeros((n, G2_WORDS), dtype=np.uint64)
+        tries = np.zeros(n, dtype=np.uint8)
+        d = np.frombuffer(dst, dtype=np.uint8) if dst else None
+        rc = fn(C.c_void_p(self._h), _p(m) if m.size else None, C.c_size_t(n), C.c_size_t(ln),
+                _p(d) if d is not None else None, C.c_size_t(len(dst)), *extra, _p(out) if n else None,
+                _p(tries) if n else None)
+        _check(rc, self, name)
+        return out, tries
+
+    def hash_to_g2(self, msgs, dst):
+        """zk_hash_to_g2 (ZKAMD-H2G2-V1): messages of one length, as a list of
+        bytes or an (n, msg_len) uint8 array, with one dst (at most 255 bytes)
+        -> ((n, 25) affine words, n uint8 try counts); a message without a
+        point has tries 0xff and zero words.  One lane per message."""
+        return self._hash_to_g2(lib().zk_hash_to_g2, "zk_hash_to_g2", msgs, dst)
+
+    def test_hash_to_g2_capped(self, msgs, dst, max_tries):
+        """zk_test_hash_to_g2_capped: the same kernel, at most max_tries tries."""
+        return self._hash_to_g2(test_lib().zk_test_hash_to_g2_capped, "zk_test_hash_to_g2_capped", msgs, dst,
+                                C.c_uint32(int(max_tries)))
+
+    def pok_verify_many(self, poks, roles, challenges):
+        """zk_pok_verify_many: n proofs ((n, 38) words: s_g1 then s_r), their
+        roles (ZK_POK_*) and 32-byte challenges -> (n uint8 ZK_POK_* statuses,
+        first_bad: the lowest index that is not ZK_POK_OK, or n).  Validation,
+        hash and pairing product run on the GPU in one call.  ValueError for a
+        role above 3."""
+        pk = np.ascontiguousarray(poks, dtype=np.uint64).reshape(-1, POK_WORDS)
+        n = len(pk)
+        ro = np.ascontiguousarray(roles, dtype=np.uint8).reshape(-1)
+        ch = _challenges(challenges, n)
+        if len(ro) != n:
+            raise ValueError("pok_verify_many: one role and one challenge per proof")
+        st = np.zeros(n, dtype=np.uint8)
+        fb = C.c_size_t(n)
+        rc = lib().zk_pok_verify_many(C.c_void_p(self._h), _p(pk) if n else None, _p(ro) if n else None,
+                                      _p(ch) if n else None, C.c_size_t(n), _p(st) if n else None, C.byref(fb))
+        _check(rc, self, "zk_pok_verify_many")
+        return st, fb.value
+
     # ---- the pairing's test hooks (include/zkp_test.h) ----
     def test_fq12(self, op, a, b=None):
         """zk_test_fq12: (n, 72) canonical words -> (n, 72)."""
@@ -1470,6 +1549,73 @@ class DeviceProvingKey:
         self.free()
 
 
+# -------------------------------------- hash to G2, proofs of knowledge ----
+def _challenges(challenges, n):
+    if isinstance(challenges, np.ndarray):
+        ch = np.ascontiguousarray(challenges, dtype=np.uint8).reshape(-1, 32)
+    else:
+        ch = np.frombuffer(b"".join(bytes(c) for c in challenges), dtype=np.uint8).reshape(-1, 32).copy()
+    if len(ch) != n:
+        raise ValueError("one 32-byte challenge per proof")
+    return ch
+
+
+def _bytes_arg(data):
+    data = bytes(data)
+    return (np.frombuffer(data, dtype=np.uint8) if data else None), len(data)
+
+
+def sha256(data):
+    """zk_sha256: the library's SHA-256 (the one under the hash to G2) -> 32 bytes."""
+    a, n = _bytes_arg(data)
+    out = np.zeros(32, dtype=np.uint8)
+    _check(lib().zk_sha256(_p(a) if n else None, C.c_size_t(n), _p(out)), None, "zk_sha256")
+    return out.tobytes()
+
+
+def hash_to_g2_host(msg, dst):
+    """zk_hash_to_g2_host: one ZKAMD-H2G2-V1 hash on the host -> (25 affine
+    words, tries).  ValueError for a dst above 255 bytes."""
+    m, ml = _bytes_arg(msg)
+    d, dl = _bytes_arg(dst)
+    out = np.zeros(G2_WORDS, dtype=np.uint64)
+    tries = C.c_uint8(0)
+    rc = lib().zk_hash_to_g2_host(_p(m) if ml else None, C.c_size_t(ml), _p(d) if dl else None, C.c_size_t(dl),
+                                  _p(out), C.byref(tries))
+    _check(rc, None, "zk_hash_to_g2_host")
+    return out, tries.value
+
+
+def _pok_c(pok):
+    w = np.ascontiguousarray(pok, dtype=np.uint64).reshape(POK_WORDS)
+    return _Pok.from_buffer_copy(w.tobytes())
+
+
+def pok_make(s, role, challenge):
+    """zk_pok_make: the proof of knowledge of 0 < s < r for a role (ZK_POK_*)
+    and a 32-byte challenge -> 38 words: [s]_1, then [s] R with R hashed from
+    challenge | compress([s]_1) | role.  ValueError for a bad share or role."""
+    s, challenge = int(s), bytes(challenge)
+    if not 0 < s < R or len(challenge) != 32 or not 0 <= int(role) <= 3:
+        raise ValueError("pok_make: a share in (0, r), a role 0..3 and a 32-byte challenge")
+    ch = np.frombuffer(challenge, dtype=np.uint8)
+    out = _Pok()
+    _check(lib().zk_pok_make(C.byref(_fr(s)), C.c_uint8(int(role)), _p(ch), C.byref(out)), None, "zk_pok_make")
+    return np.array(list(out.s_g1.w) + list(out.s_r.w), dtype=np.uint64)
+
+
+def pok_verify(pok, role, challenge):
+    """zk_pok_verify on the host -> a ZK_POK_* status (ZK_POK_OK: the proof is good)."""
+    challenge = bytes(challenge)
+    if len(challenge) != 32 or not 0 <= int(role) <= 3:
+        raise ValueError("pok_verify: a role 0..3 and a 32-byte challenge")
+    ch = np.frombuffer(challenge, dtype=np.uint8)
+    st = C.c_int(-1)
+    _check(lib().zk_pok_verify(C.byref(_pok_c(pok)), C.c_uint8(int(role)), _p(ch), C.byref(st)), None,
+           "zk_pok_verify")
+    return st.value
+
+
 class CRS:
     """crates/groth16-setup/src/lib.rs:72-78, 139-278 (GPU setup)."""
 
@@ -1583,6 +1729,41 @@ class CRS:
             C.byref(after.vk.s), _p(co) if len(co) else None, C.c_size_t(len(co)), C.byref(st))
         _check(rc, ctx, "zk_groth16_verify_contribution_sound")
         return st.value == ZK_CONTRIB_OK, st.value
+
+    # ---- phase-2 contributions with a proof of knowledge ----
+    def digest(self):
+        """zk_groth16_key_digest_sound: SHA-256 over the key's compressed points
+        (layout: include/zkp.h) -> 32 bytes; the challenge of the next
+        contribution's proof."""
+        out = np.zeros(32, dtype=np.uint8)
+        _check(lib().zk_groth16_key_digest_sound(C.byref(self.pk._bind()), C.byref(self.vk.s), _p(out)), None,
+               "zk_groth16_key_digest_sound")
+        return out.tobytes()
+
+    def contribute_proved(self, ctx, d):
+        """contribute(ctx, d) and the contributor's proof that they know d:
+        -> (new_crs, proof), proof = pok_make(d, ZK_POK_DELTA, self.digest())."""
+        new = self.contribute(ctx, d)
+        return new, pok_make(d, ZK_POK_DELTA, self.digest())
+
+    @staticmethod
+    def verify_contribution_proof(ctx, before, after, proof):
+        """Does `proof` show knowledge of the share that took delta from
+        `before` to `after`? -> (ok, status): zk_pok_verify_many on the proof
+        with the digest of `before`, then the link
+        e(s_g1, delta_2 before) e(-g1, delta_2 after) = 1 through
+        pairing_products (a failed link is ZK_POK_REJECT).  It does not replace
+        CRS.verify_contribution: a full audit runs both."""
+        pk = np.ascontiguousarray(proof, dtype=np.uint64).reshape(POK_WORDS)
+        st, _ = ctx.pok_verify_many(pk.reshape(1, -1), [ZK_POK_DELTA], [before.digest()])
+        if st[0] != ZK_POK_OK:
+            return False, int(st[0])
+        neg_g1 = np.array(to_limbs(G1_GENERATOR[0], 6) + to_limbs(FQ_MODULUS - G1_GENERATOR[1], 6) + [0],
+                          dtype=np.uint64)
+        link = ctx.pairing_products(np.stack([pk[:G1_WORDS], neg_g1]),
+                                    np.stack([before.pk.point("delta_g2"), after.pk.point("delta_g2")]), 2)
+        ok = link[0] == ZK_VERIFY_ACCEPT
+        return bool(ok), ZK_POK_OK if ok else ZK_POK_REJECT
 
     @staticmethod
     def generate_device(ctx, qap, params, num_public, shard=0, nshards=1, sound=False, vk=None):
@@ -1747,6 +1928,47 @@ class SRS:
                                               C.byref(st), C.byref(sst))
         _check(rc, ctx, "zk_srs_verify_contribution")
         return st.value == ZK_SRSC_OK, st.value, sst.value
+
+    # ---- contributions with proofs of knowledge ----
+    def digest(self):
+        """zk_srs_digest: SHA-256 over the string's compressed points (layout:
+        include/zkp.h) -> 32 bytes; the challenge of the next contribution's
+        proofs."""
+        out = np.zeros(32, dtype=np.uint8)
+        _check(lib().zk_srs_digest(C.byref(self._bind()), _p(out)), None, "zk_srs_digest")
+        return out.tobytes()
+
+    def contribute_proved(self, ctx, s, a, b):
+        """contribute(ctx, s, a, b) and the contributor's proofs that they know
+        the shares -> (new_srs, share, proof): proof a (3, 38) array, the
+        zk_pok of s, a, b with roles TAU, ALPHA, BETA and this string's
+        digest as the challenge (zk_srs_prove_contribution)."""
+        new, share = self.contribute(ctx, s, a, b)
+        pr = _SRSProof()
+        _check(lib().zk_srs_prove_contribution(C.byref(self._bind()), C.byref(_fr(s)), C.byref(_fr(a)),
+                                               C.byref(_fr(b)), C.byref(pr)), None, "zk_srs_prove_contribution")
+        proof = np.frombuffer(bytes(pr), dtype=np.uint64).reshape(3, POK_WORDS).copy()
+        return new, share, proof
+
+    @staticmethod
+    def verify_contribution_proofs(ctx, digests, shares, proofs):
+        """zk_srs_verify_contribution_proofs, the transcript check of m
+        contributions: digests m x 32 bytes (the digest of the string each
+        started from), shares (m, 3, 25) words, proofs (m, 3, 38) words ->
+        an (m, 3) uint8 array of ZK_POK_* statuses (tau, alpha, beta).  Per
+        proof: zk_pok_verify_many's check and the link to the published
+        share, both on the GPU.  It does not replace verify_contribution."""
+        sh = np.ascontiguousarray(shares, dtype=np.uint64).reshape(-1, 3, G2_WORDS)
+        pr = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 3, POK_WORDS)
+        m = len(pr)
+        dg = _challenges(digests, m)
+        if len(sh) != m:
+            raise ValueError("verify_contribution_proofs: one digest, share and proof per contribution")
+        st = np.zeros((m, 3), dtype=np.uint8)
+        rc = lib().zk_srs_verify_contribution_proofs(C.c_void_p(ctx._h), _p(dg) if m else None, _p(sh) if m else None,
+                                                     _p(pr) if m else None, C.c_size_t(m), _p(st) if m else None)
+        _check(rc, ctx, "zk_srs_verify_contribution_proofs")
+        return st
 
 
 # -------------------------------------------------------------- prove ----

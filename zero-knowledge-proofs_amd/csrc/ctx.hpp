@@ -79,6 +79,13 @@ namespace zk {
 // The proof decoder's device stage (points.hip), shared with the verification
 // that runs behind it (pairing.hip).
 void proofs_decode_launch(zk_ctx* ctx, hipStream_t st, const uint8_t* d_in, size_t m, uint64_t* d_out, uint8_t* d_pst);
+// The device stages the proofs of knowledge (hash.hip) put around the hash to
+// G2, on data already in device memory: zk_g1_validate / zk_g2_validate's
+// kernel over m ABI points (points.hip) and zk_pairing_products' kernel over m
+// products of k pairs (pairing.hip).
+void points_validate_launch(zk_ctx* ctx, hipStream_t st, bool g2, const uint64_t* d_pts, size_t m, uint8_t* d_st);
+void pairing_products_launch(zk_ctx* ctx, hipStream_t st, const uint64_t* d_g1, const uint64_t* d_g2, size_t k,
+                             size_t m, uint8_t* d_st);
 }  // namespace zk
 
 struct zk_pk_dev {

@@ -247,6 +247,16 @@ static int verify_many_run(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs,
   return ZK_OK;
 }
 
+// m products of k pairs each in device memory -> m statuses in device memory, on st
+void pairing_products_launch(zk_ctx* ctx, hipStream_t st, const uint64_t* d_g1, const uint64_t* d_g2, size_t k,
+                             size_t m, uint8_t* d_st) {
+  if (!m) return;
+  const int pi = ctx->prof.begin(st, "verify", m);
+  k_pairing_products<<<ceil_div(m, PR_BLOCK), PR_BLOCK, 0, st>>>(d_g1, d_g2, k, m, d_st);
+  ZK_LAUNCH_CHECK();
+  ctx->prof.end(st, pi);
+}
+
 static int pairing_products_run(zk_ctx* ctx, const zk_g1_affine* g1, const zk_g2_affine* g2, size_t k, size_t n,
                                 uint8_t* status) {
   if (!n) return ZK_OK;

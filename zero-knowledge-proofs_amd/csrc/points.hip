@@ -20,8 +20,6 @@
 
 namespace zk {
 
-constexpr int PT_BLOCK = 128;
-
 // 48 big-endian bytes (16-byte aligned) -> 12 little-endian words
 __device__ __forceinline__ Fq read_be48(const uint8_t* p) {
   const uint4* s = reinterpret_cast<const uint4*>(p);
@@ -287,6 +285,16 @@ int points_run(zk_ctx* ctx, const void* in, size_t n, void* out, uint8_t* status
     return ZK_ERR_ARG;
   }
   return ZK_OK;
+}
+
+// m ABI points in device memory -> m point statuses in device memory, on st
+void points_validate_launch(zk_ctx* ctx, hipStream_t st, bool g2, const uint64_t* d_pts, size_t m, uint8_t* d_st) {
+  if (!m) return;
+  const int pi = ctx->prof.begin(st, g2 ? "points_g2" : "points_g1", m);
+  if (g2) k_g2_validate<<<ceil_div(m, PT_BLOCK), PT_BLOCK, 0, st>>>(d_pts, m, d_st);
+  else k_g1_validate<<<ceil_div(m, PT_BLOCK), PT_BLOCK, 0, st>>>(d_pts, m, d_st);
+  ZK_LAUNCH_CHECK();
+  ctx->prof.end(st, pi);
 }
 
 // m compressed proofs in device memory (192 m bytes) -> m zk_proof records and

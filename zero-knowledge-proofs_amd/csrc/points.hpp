@@ -14,6 +14,11 @@
 #include "../../include/zkp.h"
 #include "curve.hpp"
 
+namespace zk {
+// lanes per block of the one-lane-per-point kernels (points.hip, hash.hip)
+constexpr int PT_BLOCK = 128;
+}  // namespace zk
+
 // ---- out-of-line products ------------------------------------------------
 // Fq operands and results travel in VGPRs (24 argument registers); the Fq2
 // product's 48 argument registers exceed the calling convention's 32, so the

@@ -8,6 +8,7 @@
 
 #include "ceremony.hpp"
 #include "ctx.hpp"
+#include "hash.hpp"
 #include "msm.hpp"
 #include "mulvec.hpp"
 #include "pairing.hpp"
@@ -795,4 +796,13 @@ int zk_test_pk_plan(const zk_pk_dev* pk, uint32_t* copies, uint32_t* sets) {
   *copies = (uint32_t)pk->copies;
   *sets = (uint32_t)((pk->win + pk->copies - 1) / pk->copies);
   return ZK_OK;
+}
+
+// ---- the hash to G2 under a try cap (hash.hip's kernel, unchanged) ----
+int zk_test_hash_to_g2_capped(zk_ctx* ctx, const uint8_t* msgs, size_t n, size_t msg_len, const uint8_t* dst,
+                              size_t dst_len, uint32_t max_tries, zk_g2_affine* out, uint8_t* tries) {
+  if (!ctx || (n && (!out || (msg_len && !msgs))) || (dst_len && !dst) || dst_len > 255 || max_tries < 1 ||
+      max_tries > H2_MAX_TRIES)
+    return ZK_ERR_ARG;
+  ZK_TGUARD(ctx, { return hash_to_g2_run(ctx, msgs, n, msg_len, dst, dst_len, max_tries, out, tries); })
 }

@@ -602,6 +602,59 @@ int zk_groth16_verify_many_bytes(zk_ctx *ctx, const zk_vk *vk, const uint8_t *pr
 int zk_groth16_verify_many_bytes_sound(zk_ctx *ctx, const zk_vk *vk, const uint8_t *proofs,
                                        const zk_fr *public_inputs, size_t n_inputs, size_t n_proofs,
                                        uint8_t *status, uint8_t *point_status);
+/* ------------------------------------------ prepared verification keys --- */
+/* A verification key prepared once and kept on the device, as arkworks'
+ * PreparedVerifyingKey / prepare_inputs and bellman's prepare_verifying_key.
+ * It holds what the batch calls above otherwise rebuild on the host per call
+ * (the Miller value of (-alpha, beta), the line tables of gamma and delta) and
+ * a window table of ic_g1[1 .. num_public]: for window width b and
+ * W = ceil(255 / b) windows (sound) or ceil(64 / b) (reference mode) the
+ * points [j 2^(b w)] ic_g1[k], j = 1 .. 2^b - 1, 96 bytes each.  b is 8 while
+ * the table stays within 512 MiB (685 inputs of a sound key), else the widest
+ * of 4, 2, 1 that does; there is no option for it.  The public-input sum of a
+ * proof is then W mixed additions per input, spread over lanes, instead of a
+ * 255-step (64-step) double-and-add per input inside the proof's lane.
+ * The mode (sound != 0: whole public inputs, one >= r malformed; 0: lo64, the
+ * reference's truncation) is fixed here, as it is for a zk_pk_dev.
+ * zk_vk_prepare validates EVERY point of the key -- alpha, beta, gamma, delta
+ * and all ic_len entries of ic_g1 -- as zk_g1_validate / zk_g2_validate do:
+ * canonical, on its curve and IN ITS SUBGROUP, which is stricter than
+ * zk_groth16_verify_many and makes every status of the prepared calls fully
+ * specified.  An identity point is accepted (an identity ic_g1 entry
+ * contributes nothing).  ZK_ERR_ARG for a bad point, zk_last_error naming it
+ * ("verification key: ic_g1[3]: not in the prime-order subgroup"), for
+ * ic_len < num_public + 1 and for a key whose table would exceed the bound at
+ * b = 1 (more than 21 931 inputs of a sound key); ZK_ERR_DEVICE on a HIP
+ * error.  The table is built on the GPU. */
+typedef struct zk_vk_dev zk_vk_dev;   /* a prepared verification key in HBM */
+int zk_vk_prepare(zk_ctx *ctx, const zk_vk *vk, int sound, zk_vk_dev **out);
+void zk_vk_dev_free(zk_vk_dev *pvk);
+/* Device memory the key holds: 4 (6676 + 24 (num_public + 1)) bytes of fixed
+ * words and the window table. */
+int zk_vk_dev_bytes(const zk_vk_dev *pvk, uint64_t *bytes);
+int zk_vk_dev_is_sound(const zk_vk_dev *pvk);   /* 1 for a key prepared with sound != 0 */
+/* ic[k] = ic_g1[0] + sum_i x_{k,i} ic_g1[i + 1] for n rows of n_inputs public
+ * inputs (row k for proof k), exactly the sum the verify kernels form: in
+ * reference mode x is lo64 of the input and lo64 = 0 contributes nothing; in
+ * sound mode x is the whole input and a row with an input >= r gets ok[k] = 0
+ * and all-zero words in ic[k] (else ok[k] = 1; ok may be NULL).  The identity
+ * is written with its infinity byte set and zero coordinates.
+ * n_inputs != the key's num_public -> ZK_ERR_INVALID_WITNESS; n == 0 -> ZK_OK.
+ * The rows cross the GPU in chunks of ZK_OPT_VERIFY_CHUNK. */
+int zk_groth16_prepare_inputs(zk_ctx *ctx, const zk_vk_dev *pvk, const zk_fr *public_inputs,
+                              size_t n_inputs, size_t n, zk_g1_affine *ic, uint8_t *ok);
+/* zk_groth16_verify_many / zk_groth16_verify_many_sound (by the key's mode)
+ * with a prepared key: per chunk the sums above, then the same verify kernel
+ * reading IC instead of forming it.  status[k] equals what the plain call
+ * gives with the key zk_vk_prepare was given; return codes as the plain call
+ * (the key's points were validated when it was prepared). */
+int zk_groth16_verify_many_prepared(zk_ctx *ctx, const zk_vk_dev *pvk, const zk_proof *proofs,
+                                    const zk_fr *public_inputs, size_t n_inputs, size_t n_proofs,
+                                    uint8_t *status);
+/* zk_groth16_verify_many_bytes / _bytes_sound with a prepared key, likewise. */
+int zk_groth16_verify_many_bytes_prepared(zk_ctx *ctx, const zk_vk_dev *pvk, const uint8_t *proofs,
+                                          const zk_fr *public_inputs, size_t n_inputs, size_t n_proofs,
+                                          uint8_t *status, uint8_t *point_status);
 /* n_products pairing products on the GPU, one lane per product: product j =
  * prod_{i<k} e(g1[jk+i], g2[jk+i]) with k = pairs_per_product; status[j] as
  * above (ACCEPT: the product is 1 -- zk_pairing_product_is_one's *result = 1;

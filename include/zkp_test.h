@@ -195,6 +195,24 @@ int zk_test_curve(zk_ctx *ctx, int field, int op, const uint32_t *p, const uint3
  * lanes that found a point earlier keeping it. */
 int zk_test_hash_to_g2_capped(zk_ctx *ctx, const uint8_t *msgs, size_t n, size_t msg_len, const uint8_t *dst,
                               size_t dst_len, uint32_t max_tries, zk_g2_affine *out, uint8_t *tries);
+/* Prepared verification keys (csrc/prepared.hpp).  The rules as pure host
+ * functions, no GPU: for a key of the mode and num_public, *width = the window
+ * width b the library chooses (0: no table fits the bound), *windows = W,
+ * *table_bytes = the window table, *dev_bytes = what zk_vk_dev_bytes reports,
+ * *bound = the table's byte bound.  With force_width in {1, 2, 4, 8} the same
+ * figures for that width instead of the chosen one (0: the rule). */
+int zk_test_prepared_plan(int sound, uint64_t num_public, int force_width, uint32_t *width, uint32_t *windows,
+                          uint64_t *table_bytes, uint64_t *dev_bytes, uint64_t *bound);
+/* *run = table additions per first-level lane of the sums for a chunk of m
+ * proofs of a key with num_public inputs and `windows` windows; *fill = the
+ * proof count from which a lane takes a whole proof. */
+int zk_test_prepared_run(uint64_t m, uint64_t num_public, uint32_t windows, uint64_t *run, uint64_t *fill);
+/* Force the window width of the keys this ctx prepares from now on (1, 2, 4,
+ * 8; 0: the rule) and the run length of every sum it computes (0: the rule).
+ * ZK_ERR_ARG for another width. */
+int zk_test_prepared_force(zk_ctx *ctx, int width, uint32_t run);
+/* The (width, windows) a prepared key holds. */
+int zk_test_prepared_info(const zk_vk_dev *pvk, uint32_t *width, uint32_t *windows);
 
 #ifdef __cplusplus
 }

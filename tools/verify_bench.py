@@ -47,6 +47,21 @@ verify_all_fold, verify_all_finish against verify; the decode phases are the
 same kernels on both sides.
 
   python tools/verify_bench.py --all
+
+--prepared: prepared verification keys (VerificationKey.prepare,
+zk_vk_prepare) in sound mode, written to profiles/verify_prepared_bench.json.
+Constructed sound keys with 1, 3, 64 and 256 public inputs (--publics) and
+full-width inputs; whole calls of Context.verify_many_bytes(sound=True) with
+the plain key -- the behaviour before prepared keys, same kernels -- and of
+the same call with the prepared key on the same bytes, alternating in one
+process.  Beside them the time of zk_vk_prepare (median of 5, and the first
+call) and the key's device bytes, and from one extra run of each under
+zk_ctx_profile the phases: verify (plain key: sums and pairings in one lane)
+against prepare_inputs and verify (prepared key).  The plain legs above
+(verify_many at every size with the 1-input key) run in the same process and
+land in the same file.
+
+  python tools/verify_bench.py --prepared
 """
 import argparse
 import importlib
@@ -153,13 +168,16 @@ def bytes_leg(zkp, ctx, vk, words, inputs, args, res):
         print("bytes_%d" % n, json.dumps(r), flush=True)
 
 
-def constructed_key(zkp, pyref, npub, count):
+def constructed_key(zkp, pyref, npub, count, key_bits=None):
     """a sound key and `count` proofs that satisfy the Groth16 equation by construction, with
-    full-width public inputs -> (vk, (count, 51) words, (count, npub, 4) inputs)"""
+    full-width public inputs -> (vk, (count, 51) words, (count, npub, 4) inputs).  key_bits: the
+    width of the key's own scalars (full by default; short ones make a long key quickly here and
+    are the same work for the GPU, which sees points)"""
     G1, G2, g1, g2, R = pyref.G1, pyref.G2, pyref.G1.gen, pyref.G2.gen, pyref.R
     rng = pyref.SplitMix64(0xA11B)
-    al, be, ga, de = (rng.fr() for _ in range(4))
-    ks = [rng.fr() for _ in range(npub + 1)]
+    sc = rng.fr if key_bits is None else (lambda: (rng.next() & ((1 << key_bits) - 1)) | 1)
+    al, be, ga, de = (sc() for _ in range(4))
+    ks = [sc() for _ in range(npub + 1)]
     vk = zkp.VerificationKey.from_points(pyref.g1_words(G1.mul(g1, al)), pyref.g2_words(G2.mul(g2, be)),
                                          pyref.g2_words(G2.mul(g2, ga)), pyref.g2_words(G2.mul(g2, de)),
                                          [pyref.g1_words(G1.mul(g1, k)) for k in ks], sound=True)
@@ -216,6 +234,57 @@ def all_leg(zkp, ctx, pyref, keys, args, res):
             print("%s_%d" % (name, n), json.dumps(r), flush=True)
 
 
+def prepared_leg(zkp, ctx, pyref, args, res):
+    """verify_many_bytes(sound=True) with the plain key against the same call with the prepared
+    key, at every size, for constructed sound keys of 1, 3, 64 and 256 public inputs (module
+    docstring)"""
+    def profiled(fn):
+        ctx.profile(1)
+        fn()
+        prof = ctx.profile_read()
+        ctx.profile(0)
+        return {ph: v["ms"] for ph, v in prof.items()}
+
+    for npub in args.publics:
+        vk, words, inputs = constructed_key(zkp, pyref, npub, 2, key_bits=40)
+        recs = np.array([np.frombuffer(zkp.Proof(w).serialize_compressed(), dtype=np.uint8) for w in words])
+        t0 = time.perf_counter()
+        pvk = vk.prepare(ctx)
+        first_ms = (time.perf_counter() - t0) * 1e3
+        pvk.free()
+        prep = timed(lambda: vk.prepare(ctx).free(), 0, 5)
+        pvk = vk.prepare(ctx)
+        key = {"num_public": npub, "zk_vk_prepare": prep, "zk_vk_prepare_first_ms": first_ms,
+               "device_bytes": pvk.device_bytes()}
+        res["prepared_key_%d" % npub] = key
+        print("prepared_key_%d" % npub, json.dumps(key), flush=True)
+        for n in args.sizes:
+            reps = -(-n // len(words))
+            data = np.ascontiguousarray(np.tile(recs, (reps, 1))[:n])
+            inp = np.ascontiguousarray(np.tile(inputs, (reps, 1, 1))[:n])
+            plain = ctx.verify_many_bytes(vk, data, inp, sound=True)
+            assert (plain == zkp.ZK_VERIFY_ACCEPT).all()
+            assert ctx.verify_many_bytes(pvk, data, inp).tobytes() == plain.tobytes()
+            wrong = inp.copy()
+            wrong[n // 2, npub - 1, 3] ^= np.uint64(1)      # one wrong public input, in its top word
+            st = ctx.verify_many_bytes(pvk, data, wrong)
+            assert st[n // 2] == zkp.ZK_VERIFY_REJECT and (np.delete(st, n // 2) == zkp.ZK_VERIFY_ACCEPT).all()
+            t = timed_alternating({"plain": lambda: ctx.verify_many_bytes(vk, data, inp, sound=True),
+                                   "prepared": lambda: ctx.verify_many_bytes(pvk, data, inp)}, args.warmup, args.runs)
+            kp = profiled(lambda: ctx.verify_many_bytes(vk, data, inp, sound=True))
+            kq = profiled(lambda: ctx.verify_many_bytes(pvk, data, inp))
+            r = {"proofs": n, "num_public": npub, "plain_key": t["plain"], "prepared_key": t["prepared"],
+                 "plain_over_prepared": t["plain"]["median_ms"] / t["prepared"]["median_ms"],
+                 "prepared_below_plain": t["prepared"]["median_ms"] < t["plain"]["median_ms"],
+                 "plain_kernel_ms": kp, "prepared_kernel_ms": kq,
+                 "plain_verify_phase_ms": kp.get("verify", 0.0),
+                 "prepared_sum_phase_ms": kq.get("prepare_inputs", 0.0),
+                 "prepared_verify_phase_ms": kq.get("verify", 0.0)}
+            res["prepared_%d_%d" % (npub, n)] = r
+            print("prepared_%d_%d" % (npub, n), json.dumps(r), flush=True)
+        pvk.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=None,
@@ -226,11 +295,16 @@ def main():
     ap.add_argument("--cpus", type=int, default=16)
     ap.add_argument("--bytes", action="store_true", help="the wire-bytes pipelines (module docstring)")
     ap.add_argument("--all", action="store_true", help="sound batch verification against verify_many_bytes_sound")
+    ap.add_argument("--prepared", action="store_true",
+                    help="verify_many_bytes_sound with the plain key against the prepared key, beside the plain legs")
+    ap.add_argument("--publics", type=int, nargs="+", default=[1, 3, 64, 256],
+                    help="--prepared: the keys' public inputs")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "verify_all_bench.json" if args.all else
-                                "verify_bytes_bench.json" if args.bytes else "verify_bench.json")
+                                "verify_bytes_bench.json" if args.bytes else
+                                "verify_prepared_bench.json" if args.prepared else "verify_bench.json")
     if args.runs < 5:
         ap.error("--runs must be at least 5")
     if args.sizes is None:
@@ -282,6 +356,8 @@ def main():
                                       "public3": constructed_key(zkp, pyref, 3, len(words))}, args, res)
         elif args.bytes:
             bytes_leg(zkp, ctx, vk, words, inputs, args, res)
+        elif args.prepared:
+            prepared_leg(zkp, ctx, pyref, args, res)
         for n in [] if args.bytes or args.all else args.sizes:
             reps = -(-n // len(words))
             w = np.ascontiguousarray(np.tile(words, (reps, 1))[:n])

@@ -67,6 +67,8 @@ EXPORTS = (
     "zk_sha256", "zk_hash_to_g2_host", "zk_hash_to_g2", "zk_pok_make", "zk_pok_verify", "zk_pok_verify_many",
     "zk_srs_digest", "zk_groth16_key_digest_sound", "zk_srs_prove_contribution",
     "zk_srs_verify_contribution_proofs",
+    "zk_vk_prepare", "zk_vk_dev_free", "zk_vk_dev_bytes", "zk_vk_dev_is_sound", "zk_groth16_prepare_inputs",
+    "zk_groth16_verify_many_prepared", "zk_groth16_verify_many_bytes_prepared",
 )
 # include/zkp_test.h (libzkp_amd_test.so)
 TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fault_after_exchange",
@@ -75,7 +77,8 @@ TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fau
                 "zk_test_verify_all_parts", "zk_test_g1_mul_scalar_plain",
                 "zk_test_g1_mul_scalars_plain", "zk_test_g2_mul_scalars_plain", "zk_test_g1_mul_scalars_table",
                 "zk_test_g2_mul_scalars_table", "zk_test_split_scalars", "zk_test_field", "zk_test_curve",
-                "zk_test_gn_walk", "zk_test_hash_to_g2_capped")
+                "zk_test_gn_walk", "zk_test_hash_to_g2_capped", "zk_test_prepared_plan", "zk_test_prepared_run",
+                "zk_test_prepared_force", "zk_test_prepared_info")
 ZK_OPT_QUOTIENT_PATH, ZK_OPT_PROVE_WIN_C, ZK_OPT_EXCHANGE_TIMEOUT_MS, ZK_OPT_DIST_QUOTIENT = 1, 2, 3, 5
 ZK_OPT_EXCHANGE_FIRST = 6
 ZK_OPT_POINT_CHUNK = 7
@@ -280,10 +283,13 @@ def lib():
                     continue
                 raise ImportError(f"{LIB_PATH} does not export {name}")
             if name not in ("zk_ctx_create", "zk_ctx_destroy", "zk_last_error",
-                            "zk_msm_bases_free", "zk_pk_free", "zk_build_id"):
+                            "zk_msm_bases_free", "zk_pk_free", "zk_build_id", "zk_vk_dev_free"):
                 f.restype = C.c_int
         L.zk_msm_bases_free.argtypes = [C.c_void_p]
         L.zk_pk_free.argtypes = [C.c_void_p]
+        if hasattr(L, "zk_vk_dev_free"):
+            L.zk_vk_dev_free.restype = None
+            L.zk_vk_dev_free.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -760,11 +766,52 @@ class Context:
         n = len(pw)
         inp = self._verify_inputs(vk, inputs, n)
         st = np.zeros(n, dtype=np.uint8)
-        fn = lib().zk_groth16_verify_many_sound if sound else lib().zk_groth16_verify_many
-        rc = fn(C.c_void_p(self._h), C.byref(vk.s), _p(pw) if n else None, _p(inp) if inp.size else None,
+        if isinstance(vk, PreparedVerificationKey):   # zk_groth16_verify_many_prepared: the mode is the key's
+            fn, key = lib().zk_groth16_verify_many_prepared, vk._handle()
+        else:
+            fn = lib().zk_groth16_verify_many_sound if sound else lib().zk_groth16_verify_many
+            key = C.byref(vk.s)
+        rc = fn(C.c_void_p(self._h), key, _p(pw) if n else None, _p(inp) if inp.size else None,
                 C.c_size_t(inp.shape[1]), C.c_size_t(n), _p(st) if n else None)
         _check(rc, self, "zk_groth16_verify_many")
         return st
+
+    # ---- prepared verification keys ----
+    def vk_prepare(self, vk, sound=None):
+        """zk_vk_prepare: validate every point of vk (subgroup included) and
+        keep its per-key words and the window table of its ic_g1 on the
+        device -> PreparedVerificationKey.  sound: the key's mode, vk.sound by
+        default.  ValueError naming a bad point."""
+        h = C.c_void_p()
+        sound = getattr(vk, "sound", False) if sound is None else bool(sound)
+        _check(lib().zk_vk_prepare(C.c_void_p(self._h), C.byref(vk.s), C.c_int(int(sound)), C.byref(h)),
+               self, "zk_vk_prepare")
+        return PreparedVerificationKey(self, h.value, vk.num_public)
+
+    def prepare_inputs(self, pvk, inputs):
+        """zk_groth16_prepare_inputs: IC = ic[0] + sum x_k ic[k + 1] for n rows
+        of public inputs ((n, n_inputs, 4) uint64, or rows of ints) -> ((n, 13)
+        uint64 words, n uint8 ok).  A sound key's row with an input >= r has
+        ok = 0 and zero words."""
+        if isinstance(inputs, np.ndarray) and inputs.ndim == 3:
+            n = len(inputs)
+        else:
+            inputs = list(inputs)
+            n = len(inputs)
+        inp = self._verify_inputs(pvk, inputs, n)
+        ic = np.zeros((n, G1_WORDS), dtype=np.uint64)
+        ok = np.zeros(n, dtype=np.uint8)
+        rc = lib().zk_groth16_prepare_inputs(C.c_void_p(self._h), pvk._handle(), _p(inp) if inp.size else None,
+                                             C.c_size_t(inp.shape[1]), C.c_size_t(n), _p(ic) if n else None,
+                                             _p(ok) if n else None)
+        _check(rc, self, "zk_groth16_prepare_inputs")
+        return ic, ok
+
+    def test_prepared_force(self, width=0, run=0):
+        """zk_test_prepared_force (test library): the window width of the keys
+        prepared from now on and the run length of every sum, 0 the rules."""
+        _check(test_lib().zk_test_prepared_force(C.c_void_p(self._h), C.c_int(width), C.c_uint32(run)), self,
+               "zk_test_prepared_force")
 
     @staticmethod
     def _proof_bytes(data, what):
@@ -802,8 +849,12 @@ class Context:
         inp = self._verify_inputs(vk, inputs, n)
         st = np.zeros(n, dtype=np.uint8)
         pst = np.zeros((n, 3), dtype=np.uint8)
-        fn = lib().zk_groth16_verify_many_bytes_sound if sound else lib().zk_groth16_verify_many_bytes
-        rc = fn(C.c_void_p(self._h), C.byref(vk.s), _p(buf) if n else None, _p(inp) if inp.size else None,
+        if isinstance(vk, PreparedVerificationKey):   # zk_groth16_verify_many_bytes_prepared
+            fn, key = lib().zk_groth16_verify_many_bytes_prepared, vk._handle()
+        else:
+            fn = lib().zk_groth16_verify_many_bytes_sound if sound else lib().zk_groth16_verify_many_bytes
+            key = C.byref(vk.s)
+        rc = fn(C.c_void_p(self._h), key, _p(buf) if n else None, _p(inp) if inp.size else None,
                 C.c_size_t(inp.shape[1]), C.c_size_t(n), _p(st) if n else None,
                 _p(pst) if n and point_status else None)
         _check(rc, self, "zk_groth16_verify_many_bytes")
@@ -1426,6 +1477,51 @@ class VerificationKey:
             _check_fields(ctx or default_context(), _key_fields(self, _VK_FIELDS), False)
         except InvalidPoint as e:
             raise SetupError(str(e)) from None
+
+    def prepare(self, ctx):
+        """Context.vk_prepare in this key's mode -> PreparedVerificationKey."""
+        return ctx.vk_prepare(self)
+
+
+class PreparedVerificationKey:
+    """A verification key prepared once and resident in HBM (zk_vk_dev), from
+    VerificationKey.prepare: Verifier.verify_many / verify_many_bytes and the
+    Context calls of those names take it in place of the key.  Its mode
+    (.sound) was fixed when it was prepared."""
+
+    def __init__(self, ctx, handle, num_public):
+        self.ctx, self._h, self.num_public = ctx, handle, num_public
+        self.sound = bool(lib().zk_vk_dev_is_sound(C.c_void_p(handle)))
+
+    def _handle(self):
+        if not getattr(self, "_h", None):
+            raise ValueError("the prepared verification key has been freed")
+        return C.c_void_p(self._h)
+
+    def device_bytes(self):
+        """zk_vk_dev_bytes: device memory the key holds (fixed words and window table)."""
+        b = C.c_uint64()
+        _check(lib().zk_vk_dev_bytes(self._handle(), C.byref(b)), None, "zk_vk_dev_bytes")
+        return b.value
+
+    def prepare_inputs(self, rows):
+        """Context.prepare_inputs with this key: ((n, 13) words of IC, n ok bytes)."""
+        return self.ctx.prepare_inputs(self, rows)
+
+    def test_info(self):
+        """zk_test_prepared_info (test library): (window width, windows)."""
+        v = [C.c_uint32() for _ in range(2)]
+        _check(test_lib().zk_test_prepared_info(self._handle(), *[C.byref(x) for x in v]), None,
+               "zk_test_prepared_info")
+        return tuple(x.value for x in v)
+
+    def free(self):
+        if getattr(self, "_h", None):
+            lib().zk_vk_dev_free(C.c_void_p(self._h))
+            self._h = None
+
+    def __del__(self):
+        self.free()
 
 
 class MsmBases:
@@ -2191,7 +2287,9 @@ class Verifier:
     """Verifier::verify (crates/groth16-core/src/lib.rs:308-355), on the host.
     A sound vk (vk.sound) goes through zk_groth16_verify_sound /
     zk_groth16_verify_many_sound: the whole public inputs, one >= r a
-    ValueError."""
+    ValueError.  verify_many and verify_many_bytes take a
+    PreparedVerificationKey (vk.prepare(ctx)) in place of vk: same results,
+    same exceptions, the key's tables made once."""
 
     @staticmethod
     def verify(vk, proof, public_inputs):

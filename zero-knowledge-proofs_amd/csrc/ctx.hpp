@@ -71,6 +71,10 @@ struct zk_ctx {
   size_t verify_chunk = (size_t)1 << 16;       // proofs / products per launch of the batch verification calls
   int gntt_map = -1;                           // group transform lanes: -1 / 1 twiddle-sharing waves, 0 twiddle per lane
   uint32_t srs_run = 0;                        // column sums over points: entries per lane, 0 the default (srs.hpp)
+  // prepared verification keys (prepared.hpp), set by the test library only: the
+  // window width of the keys made after it and the run length of the sums, 0 the rules
+  int prep_width = 0;
+  uint32_t prep_run = 0;
 
   zk::NttDomain& domain(uint32_t log_n);
 };

@@ -7,6 +7,9 @@
 // zk_groth16_verify_many_bytes puts points.hip's proof decoder in front of
 // the same kernel: ark CanonicalDeserialize (compressed, Validate::Yes) on
 // Proof, then Verifier::verify, from the proofs' 192 wire bytes.
+// zk_groth16_verify_many_prepared / _bytes_prepared run the same drivers with a
+// key prepared once (prepared.hip): its words are on the device already and
+// its window table gives every proof's IC ahead of the verify kernel.
 //
 // Per call the host prepares what every lane shares (pairing_tables): the
 // Miller value of (-alpha, beta), and for gamma and delta the PR_STEPS affine
@@ -20,16 +23,10 @@
 #include "ctx.hpp"
 #include "host_pairing.hpp"
 #include "pairing.hpp"
+#include "prepared.hpp"
 #include "verify_all.hpp"
 
 namespace zk {
-
-// the per-call words of a verification key (32-bit, device Montgomery):
-//   [VK_AB, +144)                   the Miller value of (-alpha, beta), tower order
-//   [VK_TAB, +2 x 48 PR_STEPS)      the lines of gamma, then of delta
-//   [VK_ON, +4)                     gamma finite, delta finite
-//   [VK_IC, +24 (n_inputs + 1))     ic_g1: x, y; an identity entry is (0, 0)
-constexpr size_t VK_AB = 0, VK_TAB = 144, VK_ON = VK_TAB + 2 * 48 * PR_STEPS, VK_IC = VK_ON + 4;
 
 // One lane per proof: Verifier::verify (verify.hip's zk_groth16_verify) with
 // the four Miller loops sharing their squarings.  SOUND
@@ -77,6 +74,49 @@ __global__ void __launch_bounds__(PR_BLOCK) k_groth16_verify(const uint64_t* __r
   // e(A, B) e(-IC, gamma) e(-C, delta), then the constant e(-alpha, beta)
   pr_use_g1(in, 0, A, !a_inf && !b_inf);
   pr_use_g1(in, 1, aff_neg(ic), !ic_inf && vk[VK_ON] != 0);
+  pr_use_g1(in, 2, aff_neg(Cp), !c_inf && vk[VK_ON + 1] != 0);
+  in.tab[0] = vk + VK_TAB;
+  in.tab[1] = vk + VK_TAB + 48 * PR_STEPS;
+  F12 f, g;
+  pr_miller(&f, &in);
+  f12_conj(&f, &f);
+  F2* gc = &g.c0.c0;
+#pragma unroll 1
+  for (int j = 0; j < 6; j++) gc[j] = f2_load(vk + VK_AB + 24 * j);
+  f12_mul(&f, &f, &g);
+  f12_final_exp(&f);
+  status[i] = f12_is_one(&f) ? ZK_VERIFY_ACCEPT : ZK_VERIFY_REJECT;
+}
+
+// The same check with IC given (a prepared key, prepared.hip): IC is not summed
+// here but read from sums[i] -- 24 words, (0, 0) the identity -- and in_ok[i] = 0
+// (an input out of range) makes the proof MALFORMED.  A kernel of its own and not
+// a second instance of the one above: with the body shared through an inlined
+// template the compiler laid out k_groth16_verify's scratch differently and
+// its code changed (tools/kernel_same.py), which this feature must not do.
+__global__ void __launch_bounds__(PR_BLOCK) k_groth16_verify_given(const uint64_t* __restrict__ proofs,
+                                                                   const G1A* __restrict__ sums,
+                                                                   const uint8_t* __restrict__ in_ok,
+                                                                   const uint32_t* __restrict__ vk, size_t n,
+                                                                   uint8_t* __restrict__ status) {
+  const size_t i = (size_t)blockIdx.x * PR_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t* w = proofs + PROOF_WORDS * i;
+  PrPairs in;
+  Affine<FqC> A, Cp, ic;
+  bool a_inf, b_inf, c_inf;
+  bool ok = pr_load_g1(w, &A, &a_inf);
+  ok = pr_load_g2(w + G1W, &in.Q, &b_inf) && ok;
+  ok = pr_load_g1(w + G1W + G2W, &Cp, &c_inf) && ok;
+  if (!ok || !in_ok[i]) {
+    status[i] = ZK_VERIFY_MALFORMED;
+    return;
+  }
+  const uint32_t* sw = reinterpret_cast<const uint32_t*>(sums + i);
+  ic.x = {pr_fq_load(sw)};
+  ic.y = {pr_fq_load(sw + 12)};
+  pr_use_g1(in, 0, A, !a_inf && !b_inf);
+  pr_use_g1(in, 1, aff_neg(ic), !aff_is_inf(ic) && vk[VK_ON] != 0);
   pr_use_g1(in, 2, aff_neg(Cp), !c_inf && vk[VK_ON + 1] != 0);
   in.tab[0] = vk + VK_TAB;
   in.tab[1] = vk + VK_TAB + 48 * PR_STEPS;
@@ -161,7 +201,7 @@ void line_table(const host::A2& Q, uint32_t* out) {
 }
 // Every point of the key is validated here (alpha, beta, gamma, delta and all
 // ic_len entries): false for a malformed one.
-static bool pairing_tables(const zk_vk& vk, size_t n_inputs, std::vector<uint32_t>& out) {
+bool pairing_tables(const zk_vk& vk, size_t n_inputs, std::vector<uint32_t>& out) {
   host::A1 alpha, p;
   host::A2 beta, gamma, delta;
   if (!host::load(vk.alpha_g1, alpha) || !host::load(vk.beta_g2, beta) || !host::load(vk.gamma_g2, gamma) ||
@@ -195,24 +235,33 @@ static bool pairing_tables(const zk_vk& vk, size_t n_inputs, std::vector<uint32_
 // included, and (0, 0) is on neither curve: pr_load_g1 / pr_load_g2 refuse it,
 // which makes the proof MALFORMED with the verify kernel unchanged (it does
 // not read the point statuses).
-static int verify_many_run(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs, const uint8_t* bytes,
-                           const zk_fr* inputs, size_t n_inputs, size_t n, uint8_t* status, uint8_t* point_status,
-                           bool sound) {
-  if (n_inputs != vk->num_public) return ZK_ERR_INVALID_WITNESS;
-  if (!vk->ic_g1 || vk->ic_len < n_inputs + 1) {
-    ctx->err = "verification key: ic_g1 shorter than the public inputs";
-    return ZK_ERR_ARG;
-  }
+// pvk (vk then unused): a prepared key.  Its words are on the device already,
+// its mode is the call's, and per chunk prepared.hip's sum kernels run ahead of
+// the verify kernel, which reads IC instead of summing it.
+static int verify_many_run(zk_ctx* ctx, const zk_vk* vk, const zk_vk_dev* pvk, const zk_proof* proofs,
+                           const uint8_t* bytes, const zk_fr* inputs, size_t n_inputs, size_t n, uint8_t* status,
+                           uint8_t* point_status, bool sound) {
+  if (n_inputs != (pvk ? pvk->num_public : vk->num_public)) return ZK_ERR_INVALID_WITNESS;
   std::vector<uint32_t> tables;
-  if (!pairing_tables(*vk, n_inputs, tables)) {
-    ctx->err = "verification key: a point is not canonical or not on its curve";
+  if (!pvk) {
+    if (!vk->ic_g1 || vk->ic_len < n_inputs + 1) {
+      ctx->err = "verification key: ic_g1 shorter than the public inputs";
+      return ZK_ERR_ARG;
+    }
+    if (!pairing_tables(*vk, n_inputs, tables)) {
+      ctx->err = "verification key: a point is not canonical or not on its curve";
+      return ZK_ERR_ARG;
+    }
+  } else if (pvk->device != ctx->device) {
+    ctx->err = "prepared verification key: made on another device";
     return ZK_ERR_ARG;
   }
   if (!n) return ZK_OK;
   hipStream_t st = ctx->stream;
   const size_t chunk = std::min<size_t>(ctx->verify_chunk, n), in_sz = sizeof(zk_fr) * n_inputs;
   DevBuf d_vk, d_proofs, d_in, d_st, d_bytes, d_pst;
-  d_vk.ensure(4 * tables.size());
+  PrepWork sums;
+  if (!pvk) d_vk.ensure(4 * tables.size());
   d_proofs.ensure(sizeof(zk_proof) * chunk);
   d_in.ensure(std::max<size_t>(in_sz * chunk, 16));
   d_st.ensure(chunk);
@@ -220,7 +269,7 @@ static int verify_many_run(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs,
     d_bytes.ensure(192 * chunk);
     d_pst.ensure(3 * chunk);
   }
-  ZK_HIP(hipMemcpyAsync(d_vk.p, tables.data(), 4 * tables.size(), hipMemcpyHostToDevice, st));
+  if (!pvk) ZK_HIP(hipMemcpyAsync(d_vk.p, tables.data(), 4 * tables.size(), hipMemcpyHostToDevice, st));
   for (size_t lo = 0; lo < n; lo += chunk) {
     const size_t m = std::min(chunk, n - lo);
     if (bytes) {
@@ -230,8 +279,13 @@ static int verify_many_run(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs,
       ZK_HIP(hipMemcpyAsync(d_proofs.p, proofs + lo, sizeof(zk_proof) * m, hipMemcpyHostToDevice, st));
     }
     if (in_sz) ZK_HIP(hipMemcpyAsync(d_in.p, inputs + n_inputs * lo, in_sz * m, hipMemcpyHostToDevice, st));
+    if (pvk) prepared_sums_launch(ctx, st, pvk, d_in.as<uint64_t>(), m, sums);
     const int pi = ctx->prof.begin(st, "verify", m);
-    if (sound)
+    if (pvk)
+      k_groth16_verify_given<<<ceil_div(m, PR_BLOCK), PR_BLOCK, 0, st>>>(
+          d_proofs.as<uint64_t>(), sums.ic.as<G1A>(), sums.ok.as<uint8_t>(), pvk->words.as<uint32_t>(), m,
+          d_st.as<uint8_t>());
+    else if (sound)
       k_groth16_verify<true><<<ceil_div(m, PR_BLOCK), PR_BLOCK, 0, st>>>(
           d_proofs.as<uint64_t>(), d_in.as<uint64_t>(), n_inputs, d_vk.as<uint32_t>(), m, d_st.as<uint8_t>());
     else
@@ -304,28 +358,49 @@ int zk_groth16_verify_many(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs,
                            size_t n_inputs, size_t n_proofs, uint8_t* status) {
   if (!ctx || !vk || (n_proofs && (!proofs || !status || (n_inputs && !public_inputs)))) return ZK_ERR_ARG;
   ZK_PGUARD(ctx, {
-    return verify_many_run(ctx, vk, proofs, nullptr, public_inputs, n_inputs, n_proofs, status, nullptr, false);
+    return verify_many_run(ctx, vk, nullptr, proofs, nullptr, public_inputs, n_inputs, n_proofs, status, nullptr,
+                           false);
   })
 }
 int zk_groth16_verify_many_sound(zk_ctx* ctx, const zk_vk* vk, const zk_proof* proofs, const zk_fr* public_inputs,
                                  size_t n_inputs, size_t n_proofs, uint8_t* status) {
   if (!ctx || !vk || (n_proofs && (!proofs || !status || (n_inputs && !public_inputs)))) return ZK_ERR_ARG;
   ZK_PGUARD(ctx, {
-    return verify_many_run(ctx, vk, proofs, nullptr, public_inputs, n_inputs, n_proofs, status, nullptr, true);
+    return verify_many_run(ctx, vk, nullptr, proofs, nullptr, public_inputs, n_inputs, n_proofs, status, nullptr, true);
   })
 }
 int zk_groth16_verify_many_bytes(zk_ctx* ctx, const zk_vk* vk, const uint8_t* proofs, const zk_fr* public_inputs,
                                  size_t n_inputs, size_t n_proofs, uint8_t* status, uint8_t* point_status) {
   if (!ctx || !vk || (n_proofs && (!proofs || !status || (n_inputs && !public_inputs)))) return ZK_ERR_ARG;
   ZK_PGUARD(ctx, {
-    return verify_many_run(ctx, vk, nullptr, proofs, public_inputs, n_inputs, n_proofs, status, point_status, false);
+    return verify_many_run(ctx, vk, nullptr, nullptr, proofs, public_inputs, n_inputs, n_proofs, status, point_status,
+                           false);
   })
 }
 int zk_groth16_verify_many_bytes_sound(zk_ctx* ctx, const zk_vk* vk, const uint8_t* proofs, const zk_fr* public_inputs,
                                        size_t n_inputs, size_t n_proofs, uint8_t* status, uint8_t* point_status) {
   if (!ctx || !vk || (n_proofs && (!proofs || !status || (n_inputs && !public_inputs)))) return ZK_ERR_ARG;
   ZK_PGUARD(ctx, {
-    return verify_many_run(ctx, vk, nullptr, proofs, public_inputs, n_inputs, n_proofs, status, point_status, true);
+    return verify_many_run(ctx, vk, nullptr, nullptr, proofs, public_inputs, n_inputs, n_proofs, status, point_status,
+                           true);
+  })
+}
+// the same drivers with a prepared key: the mode is the key's
+int zk_groth16_verify_many_prepared(zk_ctx* ctx, const zk_vk_dev* pvk, const zk_proof* proofs,
+                                    const zk_fr* public_inputs, size_t n_inputs, size_t n_proofs, uint8_t* status) {
+  if (!ctx || !pvk || (n_proofs && (!proofs || !status || (n_inputs && !public_inputs)))) return ZK_ERR_ARG;
+  ZK_PGUARD(ctx, {
+    return verify_many_run(ctx, nullptr, pvk, proofs, nullptr, public_inputs, n_inputs, n_proofs, status, nullptr,
+                           pvk->sound);
+  })
+}
+int zk_groth16_verify_many_bytes_prepared(zk_ctx* ctx, const zk_vk_dev* pvk, const uint8_t* proofs,
+                                          const zk_fr* public_inputs, size_t n_inputs, size_t n_proofs,
+                                          uint8_t* status, uint8_t* point_status) {
+  if (!ctx || !pvk || (n_proofs && (!proofs || !status || (n_inputs && !public_inputs)))) return ZK_ERR_ARG;
+  ZK_PGUARD(ctx, {
+    return verify_many_run(ctx, nullptr, pvk, nullptr, proofs, public_inputs, n_inputs, n_proofs, status,
+                           point_status, pvk->sound);
   })
 }
 int zk_pairing_products(zk_ctx* ctx, const zk_g1_affine* g1, const zk_g2_affine* g2, size_t pairs_per_product,

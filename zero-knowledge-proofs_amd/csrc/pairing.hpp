@@ -28,6 +28,8 @@
 // The device therefore computes f^(PR_FINAL_EXP_C (p^12 - 1) / r) with
 // PR_FINAL_EXP_C = 3; 3 is coprime to r, so "== 1" is the host's verdict.
 #pragma once
+#include <vector>
+
 #include "points.hpp"
 
 constexpr int PR_FINAL_EXP_C = 3;
@@ -446,5 +448,17 @@ ZK_DI Affine<FqC> pr_g1_affine(const XYZZ<FqC>& p) {
   const FqC i2 = f_sqr(f_mul(p.ZZ, i3));
   return {f_mul(p.X, i2), f_mul(p.Y, i3)};
 }
+
+// ---- the per-key words the verify kernels read (pairing.hip, prepared.hip) ------------
+// 32-bit words, device Montgomery:
+//   [VK_AB, +144)                   the Miller value of (-alpha, beta), tower order
+//   [VK_TAB, +2 x 48 PR_STEPS)      the lines of gamma, then of delta
+//   [VK_ON, +4)                     gamma finite, delta finite
+//   [VK_IC, +24 (n_inputs + 1))     ic_g1: x, y; an identity entry is (0, 0)
+constexpr size_t VK_AB = 0, VK_TAB = 144, VK_ON = VK_TAB + 2 * 48 * PR_STEPS, VK_IC = VK_ON + 4;
+// Those words for a key, made on the host (pairing.hip).  Every point of the
+// key is validated -- canonical and on its curve -- alpha, beta, gamma, delta
+// and all ic_len entries: false for a malformed one.
+bool pairing_tables(const zk_vk& vk, size_t n_inputs, std::vector<uint32_t>& out);
 
 }  // namespace zk

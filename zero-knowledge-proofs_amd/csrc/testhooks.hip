@@ -13,6 +13,7 @@
 #include "mulvec.hpp"
 #include "pairing.hpp"
 #include "points.hpp"
+#include "prepared.hpp"
 #include "prove.hpp"
 #include "setup.hpp"
 #include "verify_all.hpp"
@@ -805,4 +806,36 @@ int zk_test_hash_to_g2_capped(zk_ctx* ctx, const uint8_t* msgs, size_t n, size_t
       max_tries > H2_MAX_TRIES)
     return ZK_ERR_ARG;
   ZK_TGUARD(ctx, { return hash_to_g2_run(ctx, msgs, n, msg_len, dst, dst_len, max_tries, out, tries); })
+}
+
+// ---- prepared verification keys: the rules, and their overrides ----
+int zk_test_prepared_plan(int sound, uint64_t num_public, int force_width, uint32_t* width, uint32_t* windows,
+                          uint64_t* table_bytes, uint64_t* dev_bytes, uint64_t* bound) {
+  if (!width || !windows || !table_bytes || !dev_bytes || !bound) return ZK_ERR_ARG;
+  if (force_width != 0 && force_width != 1 && force_width != 2 && force_width != 4 && force_width != 8) return ZK_ERR_ARG;
+  const int b = force_width ? force_width : prep_width(sound != 0, num_public);
+  *width = (uint32_t)b;
+  *windows = b ? (uint32_t)prep_windows(sound != 0, b) : 0;
+  *table_bytes = b ? prep_table_bytes(sound != 0, num_public, b) : 0;
+  *dev_bytes = 4 * prep_words(num_public) + *table_bytes;
+  *bound = PREP_TABLE_MAX;
+  return ZK_OK;
+}
+int zk_test_prepared_run(uint64_t m, uint64_t num_public, uint32_t windows, uint64_t* run, uint64_t* fill) {
+  if (!run || !fill) return ZK_ERR_ARG;
+  *run = prep_run_len(m, num_public, (int)windows);
+  *fill = PREP_FILL;
+  return ZK_OK;
+}
+int zk_test_prepared_force(zk_ctx* ctx, int width, uint32_t run) {
+  if (!ctx || (width != 0 && width != 1 && width != 2 && width != 4 && width != 8)) return ZK_ERR_ARG;
+  ctx->prep_width = width;
+  ctx->prep_run = run;
+  return ZK_OK;
+}
+int zk_test_prepared_info(const zk_vk_dev* pvk, uint32_t* width, uint32_t* windows) {
+  if (!pvk || !width || !windows) return ZK_ERR_ARG;
+  *width = (uint32_t)pvk->width;
+  *windows = (uint32_t)pvk->windows;
+  return ZK_OK;
 }

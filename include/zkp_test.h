@@ -213,6 +213,49 @@ int zk_test_prepared_run(uint64_t m, uint64_t num_public, uint32_t windows, uint
 int zk_test_prepared_force(zk_ctx *ctx, int width, uint32_t run);
 /* The (width, windows) a prepared key holds. */
 int zk_test_prepared_info(const zk_vk_dev *pvk, uint32_t *width, uint32_t *windows);
+/* MSM chunking (csrc/msm.hip).  The accumulate splits the M grouped entries
+ * of an MSM over T units, chunks of K = ceil(M / T) rounded up to a multiple
+ * of 4 (4 when M = 0); a bucket over more than fix_max chunks goes to the merge
+ * levels instead of the serial fixup.  T is by rule one full-occupancy round
+ * of the chip, so small inputs only ever see K = 4.  Force both for every MSM
+ * this ctx launches from now on -- its five prove workspaces and the two of
+ * the first part of a host witness: T = 0 the rule, else 1 .. 2^22 units;
+ * fix_max = 0 the rule (8), else >= 1.  Host values only, the kernels are the
+ * shipped ones.  ZK_ERR_ARG for a T above 2^22.  A test restores (0, 0). */
+int zk_test_msm_force(zk_ctx *ctx, uint32_t T, uint32_t fix_max);
+/* What the last finished MSM of workspace `which` ran with: which = 0 .. 4 the
+ * prove slots (pi_A, pi_B, B1, IC, H; zk_msm_* use 0; the A + B1 batch is 0,
+ * IC + H is 4), 5 and 6 the G2 and the A + B1 workspace of a host witness's
+ * first part.  info[ZK_TEST_MSM_*], ZK_TEST_MSM_WORDS words: the plan (C window
+ * bits, NWIN, BITS, SW words per scalar, SHARED, COPIES, NRED reduction
+ * windows, NSEG, SEGSHIFT, G buckets, T, FIX_MAX, N points), and read back
+ * from the device M = off[G], the grouped entries (a per-window plan: the
+ * non-zero digits), and NBIG = the buckets the fixup left to the merge
+ * (zeroed by the grouping, counted by the fixup, not written after it).
+ * NATURAL_T = the rule's T for the curve g2 (0: G1, 1: G2), whatever is
+ * forced.  Waits for the ctx's streams.  ZK_ERR_ARG for a workspace no MSM
+ * has run on. */
+enum { ZK_TEST_MSM_C = 0, ZK_TEST_MSM_NWIN = 1, ZK_TEST_MSM_BITS = 2, ZK_TEST_MSM_SW = 3, ZK_TEST_MSM_SHARED = 4,
+       ZK_TEST_MSM_COPIES = 5, ZK_TEST_MSM_NRED = 6, ZK_TEST_MSM_NSEG = 7, ZK_TEST_MSM_SEGSHIFT = 8,
+       ZK_TEST_MSM_G = 9, ZK_TEST_MSM_T = 10, ZK_TEST_MSM_FIX_MAX = 11, ZK_TEST_MSM_M = 12, ZK_TEST_MSM_NBIG = 13,
+       ZK_TEST_MSM_NATURAL_T = 14, ZK_TEST_MSM_N = 15, ZK_TEST_MSM_WORDS = 16 };
+int zk_test_msm_info(zk_ctx *ctx, int which, int g2, uint32_t *info);
+/* The grouping of that MSM (csrc/group.hip) as the accumulate read it: *G and
+ * *M as above, and with cap >= max(*G + 1, *M): off_out[0 .. G] = the first
+ * entry of every bucket (off[G] = M), key_out[0 .. M) = the sorted bucket of
+ * every entry, ent_out[0 .. M) = its base index with the digit's sign in bit
+ * 31 (0x7fffffff: the dummy entry of a zero digit in a shared plan).  cap = 0
+ * only queries the sizes. */
+int zk_test_msm_grouping(zk_ctx *ctx, int which, uint32_t *off_out, uint32_t *key_out, uint32_t *ent_out,
+                         size_t cap, size_t *G, size_t *M);
+/* Overwrite what the MSMs of this ctx left in their workspaces -- buckets,
+ * chunk partials, merge slots, row/column sums and quantities of the seven
+ * workspaces above -- with the byte 0xA5: no coordinate is below p and no
+ * point is the identity.  An MSM writes every value it later reads, so this
+ * changes no result; a test calls it before an MSM so that a bucket or a
+ * partial the MSM fails to write cannot pass on the right value an earlier
+ * MSM of the same inputs left there.  Waits for the ctx's streams. */
+int zk_test_msm_scrub(zk_ctx *ctx);
 
 #ifdef __cplusplus
 }

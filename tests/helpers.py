@@ -42,3 +42,22 @@ def constraints_of(case):
 def proof_words(case):
     p = case["proof"]
     return g1_words(p["a"]) + g2_words(p["b"]) + g1_words(p["c"])
+
+
+def skewed_witness(n, kind, seed):
+    """x_i, y_i drawn from a tiny set, z_i = x_i y_i (the synthetic circuit's
+    rows hold for any x, y): most digits of the lo64 scalars then fall in a
+    handful of buckets."""
+    rng = np.random.default_rng(seed)
+    if kind == "bits":
+        x, y = rng.integers(0, 2, n), rng.integers(0, 2, n)
+    elif kind == "small":
+        x, y = rng.integers(0, 4, n), rng.integers(0, 4, n)
+    else:   # "ones": every x, y, z equal to 1
+        x, y = np.ones(n, dtype=np.int64), np.ones(n, dtype=np.int64)
+    z = np.zeros((3 * n + 1, 4), dtype=np.uint64)
+    z[0, 0] = 1
+    z[1::3, 0] = x.astype(np.uint64)
+    z[2::3, 0] = y.astype(np.uint64)
+    z[3::3, 0] = (x * y).astype(np.uint64)
+    return z

@@ -10,6 +10,8 @@ so they are only reproducible if the order inside every bucket is."""
 import numpy as np
 import pytest
 
+from helpers import skewed_witness as _skewed_witness
+
 pytestmark = pytest.mark.gpu
 
 
@@ -21,25 +23,6 @@ def _circuit(zkp, oracle, log_n, seed):
     params = [rng.fr() for _ in range(5)]
     r, s = rng.fr(), rng.fr()
     return n, qap, csr_o, params, r, s
-
-
-def _skewed_witness(n, kind, seed):
-    """x_i, y_i drawn from a tiny set, z_i = x_i y_i (the synthetic circuit's
-    rows hold for any x, y): most digits of the lo64 scalars then fall in a
-    handful of buckets."""
-    rng = np.random.default_rng(seed)
-    if kind == "bits":
-        x, y = rng.integers(0, 2, n), rng.integers(0, 2, n)
-    elif kind == "small":
-        x, y = rng.integers(0, 4, n), rng.integers(0, 4, n)
-    else:   # "ones": every x, y, z equal to 1
-        x, y = np.ones(n, dtype=np.int64), np.ones(n, dtype=np.int64)
-    z = np.zeros((3 * n + 1, 4), dtype=np.uint64)
-    z[0, 0] = 1
-    z[1::3, 0] = x.astype(np.uint64)
-    z[2::3, 0] = y.astype(np.uint64)
-    z[3::3, 0] = (x * y).astype(np.uint64)
-    return z
 
 
 @pytest.mark.parametrize("kind", ["bits", "small", "ones"])

@@ -78,7 +78,12 @@ TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fau
                 "zk_test_g1_mul_scalars_plain", "zk_test_g2_mul_scalars_plain", "zk_test_g1_mul_scalars_table",
                 "zk_test_g2_mul_scalars_table", "zk_test_split_scalars", "zk_test_field", "zk_test_curve",
                 "zk_test_gn_walk", "zk_test_hash_to_g2_capped", "zk_test_prepared_plan", "zk_test_prepared_run",
-                "zk_test_prepared_force", "zk_test_prepared_info")
+                "zk_test_prepared_force", "zk_test_prepared_info", "zk_test_msm_force", "zk_test_msm_info",
+                "zk_test_msm_grouping", "zk_test_msm_scrub")
+# words of zk_test_msm_info (include/zkp_test.h), and its workspaces beside the five prove slots
+TEST_MSM_INFO = ("c", "nwin", "bits", "sw", "shared", "copies", "nred", "nseg", "segshift", "G", "T", "fix_max",
+                 "M", "nbig", "natural_T", "n")
+TEST_MSM_PART_G2, TEST_MSM_PART_ABI = 5, 6
 ZK_OPT_QUOTIENT_PATH, ZK_OPT_PROVE_WIN_C, ZK_OPT_EXCHANGE_TIMEOUT_MS, ZK_OPT_DIST_QUOTIENT = 1, 2, 3, 5
 ZK_OPT_EXCHANGE_FIRST = 6
 ZK_OPT_POINT_CHUNK = 7
@@ -812,6 +817,38 @@ class Context:
         prepared from now on and the run length of every sum, 0 the rules."""
         _check(test_lib().zk_test_prepared_force(C.c_void_p(self._h), C.c_int(width), C.c_uint32(run)), self,
                "zk_test_prepared_force")
+
+    def test_msm_force(self, T=0, fix_max=0):
+        """zk_test_msm_force (test library): the accumulate units and the fixup
+        threshold of every MSM this context launches from now on, 0 the rules."""
+        _check(test_lib().zk_test_msm_force(C.c_void_p(self._h), C.c_uint32(T), C.c_uint32(fix_max)), self,
+               "zk_test_msm_force")
+
+    def test_msm_scrub(self):
+        """zk_test_msm_scrub (test library): overwrite what earlier MSMs left in
+        this context's MSM workspaces, so that no MSM can pass on stale sums."""
+        _check(test_lib().zk_test_msm_scrub(C.c_void_p(self._h)), self, "zk_test_msm_scrub")
+
+    def test_msm_info(self, which=0, g2=False):
+        """zk_test_msm_info (test library): {name: value} over TEST_MSM_INFO for
+        the last finished MSM of workspace `which`."""
+        v = (C.c_uint32 * len(TEST_MSM_INFO))()
+        _check(test_lib().zk_test_msm_info(C.c_void_p(self._h), C.c_int(which), C.c_int(1 if g2 else 0), v), self,
+               "zk_test_msm_info")
+        return dict(zip(TEST_MSM_INFO, (int(x) for x in v)))
+
+    def test_msm_grouping(self, which=0):
+        """zk_test_msm_grouping (test library): (off[0..G], key[0..M), ent[0..M))
+        of the last finished MSM of workspace `which`, uint32 arrays."""
+        G, M = C.c_size_t(), C.c_size_t()
+        fn = test_lib().zk_test_msm_grouping
+        _check(fn(C.c_void_p(self._h), C.c_int(which), None, None, None, C.c_size_t(0), C.byref(G), C.byref(M)),
+               self, "zk_test_msm_grouping")
+        cap = max(G.value + 1, M.value)
+        off, key, ent = (np.zeros(cap, dtype=np.uint32) for _ in range(3))
+        _check(fn(C.c_void_p(self._h), C.c_int(which), _p(off), _p(key), _p(ent), C.c_size_t(cap), C.byref(G),
+                  C.byref(M)), self, "zk_test_msm_grouping")
+        return off[:G.value + 1], key[:M.value], ent[:M.value]
 
     @staticmethod
     def _proof_bytes(data, what):

@@ -746,6 +746,11 @@ static uint32_t accum_threads() {
   return T;
 }
 
+template <class C>
+uint32_t msm_accum_units() {
+  return accum_threads<C>();
+}
+
 // Blocks of the merge kernel the chip holds at once: the upper bound of its
 // grid-barrier launch.
 template <class C>
@@ -838,8 +843,8 @@ static void msm_front_impl(MsmWork& w, const MsmSeg* segs, int nseg, int sw, hip
   w.ent.ensure(sizeof(uint32_t) * (M + ENTQ));   // EntQ reads up to ENTQ - 1 past the end
   w.key.ensure(sizeof(uint32_t) * (M + ENTQ));
   w.buckets.ensure(sizeof(X) * p.G);
-  p.T = accum_threads<C>();
-  p.fix_max = MSM_FIX_MAX;
+  p.T = w.force_T ? w.force_T : accum_threads<C>();
+  p.fix_max = w.force_fix_max ? w.force_fix_max : MSM_FIX_MAX;
   // row/column sums: G2 on lane pairs, G1 one lane per add (lane-quad tail),
   // split to fill the chip.  Round 5: the H MSM's 512 sums moved from lane
   // quads (4 waves per sum) to this form, bucket sum 0.285 -> 0.246 ms serial
@@ -1212,6 +1217,7 @@ void host_to_abi<G2>(const host::X<host::Fq2>& p, uint64_t* w) {
 }
 
 #define ZK_MSM_INST(C)                                                                               \
+  template uint32_t msm_accum_units<C>();                                                            \
   template void msm_launch<C>(MsmWork&, const C::A*, const uint64_t*, int, uint32_t, int, hipStream_t,  \
                               uint32_t);                                                              \
   template void msm_launch_grouped<C>(MsmWork&, const C::A*, const uint64_t*, int, uint32_t, int, int,  \

@@ -141,7 +141,17 @@ struct MsmWork {
   MsmPlan plan{};
   Prof* prof = nullptr;  // optional live kernel timing
   std::string tag;      // phase-name prefix (per-MSM profiling)
+  // test library only (zk_test_msm_force): the plan's T and fix_max of every
+  // MSM launched on this workspace from now on, 0 = the rule
+  // (msm_accum_units, MSM_FIX_MAX).  Host values only: the kernels take both
+  // as arguments already.
+  uint32_t force_T = 0, force_fix_max = 0;
 };
+
+// The accumulate units T of the rule: one full-occupancy round of the chip
+// for the curve (what MsmPlan::T is unless MsmWork::force_T says otherwise).
+template <class C>
+uint32_t msm_accum_units();
 
 // Launch the device part of an MSM over n Montgomery-affine device bases and
 // n scalars of `sw` u64 words each (canonical little-endian, < 2^bits).

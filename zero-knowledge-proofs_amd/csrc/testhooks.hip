@@ -839,3 +839,109 @@ int zk_test_prepared_info(const zk_vk_dev* pvk, uint32_t* width, uint32_t* windo
   *windows = (uint32_t)pvk->windows;
   return ZK_OK;
 }
+
+// ---- MSM chunking: the accumulate units and the fixup threshold under a
+// test's control, and readbacks of what the last MSM of a workspace did ----
+namespace zk {
+// works 0..4: ctx->msm[], 5: part_g2[0], 6: part_abi[0]
+static MsmWork* test_msm_work(zk_ctx* ctx, int which) {
+  if (which >= 0 && which < NUM_MSM) return &ctx->msm[which];
+  if (which == NUM_MSM) return &ctx->part_g2[0];
+  if (which == NUM_MSM + 1) return &ctx->part_abi[0];
+  return nullptr;
+}
+// every stream an MSM of this ctx may still run on
+static void test_msm_sync(zk_ctx* ctx) {
+  ZK_HIP(hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < NUM_SIDE; k++)
+    if (ctx->side[k]) ZK_HIP(hipStreamSynchronize(ctx->side[k]));
+}
+// a workspace that has run an MSM: its plan and its device arrays exist
+static bool test_msm_ran(const MsmWork& w) { return w.plan.G && w.off.p && w.nbig.p && w.key.p && w.ent.p; }
+}  // namespace zk
+
+int zk_test_msm_force(zk_ctx* ctx, uint32_t T, uint32_t fix_max) {
+  if (!ctx || T > (1u << 22)) return ZK_ERR_ARG;
+  for (int k = 0; k < NUM_MSM; k++) {
+    ctx->msm[k].force_T = T;
+    ctx->msm[k].force_fix_max = fix_max;
+  }
+  for (int k = 0; k < HOST_PARTS - 1; k++) {
+    ctx->part_g2[k].force_T = ctx->part_abi[k].force_T = T;
+    ctx->part_g2[k].force_fix_max = ctx->part_abi[k].force_fix_max = fix_max;
+  }
+  return ZK_OK;
+}
+
+int zk_test_msm_info(zk_ctx* ctx, int which, int g2, uint32_t* info) {
+  if (!ctx || !info || (g2 != 0 && g2 != 1)) return ZK_ERR_ARG;
+  MsmWork* w = test_msm_work(ctx, which);
+  if (!w) return ZK_ERR_ARG;
+  ZK_TGUARD(ctx, {
+    if (!test_msm_ran(*w)) throw Error(ZK_ERR_ARG, "test_msm_info: no MSM has run on this workspace");
+    const MsmPlan& p = w->plan;
+    test_msm_sync(ctx);
+    uint32_t M = 0, nbig = 0;
+    ZK_HIP(hipMemcpy(&M, w->off.as<uint32_t>() + p.G, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    ZK_HIP(hipMemcpy(&nbig, w->nbig.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    info[ZK_TEST_MSM_C] = (uint32_t)p.c;
+    info[ZK_TEST_MSM_NWIN] = (uint32_t)p.nwin;
+    info[ZK_TEST_MSM_BITS] = (uint32_t)p.bits;
+    info[ZK_TEST_MSM_SW] = (uint32_t)p.sw;
+    info[ZK_TEST_MSM_SHARED] = (uint32_t)p.shared;
+    info[ZK_TEST_MSM_COPIES] = (uint32_t)p.copies;
+    info[ZK_TEST_MSM_NRED] = p.nred;
+    info[ZK_TEST_MSM_NSEG] = (uint32_t)p.nseg;
+    info[ZK_TEST_MSM_SEGSHIFT] = p.segshift;
+    info[ZK_TEST_MSM_G] = p.G;
+    info[ZK_TEST_MSM_T] = p.T;
+    info[ZK_TEST_MSM_FIX_MAX] = p.fix_max;
+    info[ZK_TEST_MSM_M] = M;
+    info[ZK_TEST_MSM_NBIG] = nbig;
+    info[ZK_TEST_MSM_NATURAL_T] = g2 ? msm_accum_units<G2>() : msm_accum_units<G1>();
+    info[ZK_TEST_MSM_N] = p.n;
+    return ZK_OK;
+  })
+}
+
+int zk_test_msm_grouping(zk_ctx* ctx, int which, uint32_t* off_out, uint32_t* key_out, uint32_t* ent_out, size_t cap,
+                         size_t* G, size_t* M) {
+  if (!ctx || !G || !M) return ZK_ERR_ARG;
+  MsmWork* w = test_msm_work(ctx, which);
+  if (!w) return ZK_ERR_ARG;
+  ZK_TGUARD(ctx, {
+    if (!test_msm_ran(*w)) throw Error(ZK_ERR_ARG, "test_msm_grouping: no MSM has run on this workspace");
+    const uint32_t g = w->plan.G;
+    test_msm_sync(ctx);
+    uint32_t m = 0;
+    ZK_HIP(hipMemcpy(&m, w->off.as<uint32_t>() + g, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *G = g;
+    *M = m;
+    if (!cap) return ZK_OK;
+    if (cap < (size_t)g + 1 || cap < m || !off_out || !key_out || !ent_out) return ZK_ERR_ARG;
+    // off[G] never exceeds the entries the front sized key / ent for
+    if (sizeof(uint32_t) * (size_t)m > w->key.bytes || sizeof(uint32_t) * (size_t)m > w->ent.bytes ||
+        sizeof(uint32_t) * ((size_t)g + 1) > w->off.bytes)
+      throw Error(ZK_ERR_DEVICE, "test_msm_grouping: off[G] exceeds the workspace");
+    ZK_HIP(hipMemcpy(off_out, w->off.p, sizeof(uint32_t) * ((size_t)g + 1), hipMemcpyDeviceToHost));
+    if (m) {
+      ZK_HIP(hipMemcpy(key_out, w->key.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+      ZK_HIP(hipMemcpy(ent_out, w->ent.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+    }
+    return ZK_OK;
+  })
+}
+
+int zk_test_msm_scrub(zk_ctx* ctx) {
+  if (!ctx) return ZK_ERR_ARG;
+  ZK_TGUARD(ctx, {
+    test_msm_sync(ctx);
+    for (int which = 0; which < NUM_MSM + 2; which++) {
+      MsmWork* w = test_msm_work(ctx, which);
+      for (DevBuf* b : {&w->buckets, &w->partials, &w->partials2, &w->rc, &w->res})
+        if (b->p && b->bytes) ZK_HIP(hipMemset(b->p, 0xA5, b->bytes));
+    }
+    ZK_HIP(hipDeviceSynchronize());
+    return ZK_OK;
+  })
+}

@@ -856,6 +856,63 @@ typedef enum { ZK_SRS_OK = 0, ZK_SRS_SHAPE, ZK_SRS_POINT, ZK_SRS_GENERATOR, ZK_S
                ZK_SRS_POWERS_G2, ZK_SRS_ALPHA, ZK_SRS_BETA } zk_srs_status;
 int zk_srs_verify(zk_ctx *ctx, const zk_srs *srs, const zk_fr *coeffs, size_t n_coeffs, int *status);
 
+/* ------------------------------------------------ a key against its string --- */
+/* Is (pk, vk) the sound key of the circuit qap over the string srs, for SOME
+ * delta and gamma = 1 (what zk_groth16_setup_srs_sound makes, after any number
+ * of zk_groth16_contribute_sound)?  The step that joins the two phases of a
+ * ceremony, without rebuilding the key: no group transform, and nothing but
+ * the final key is needed.  No reference counterpart.
+ *
+ * With V = num_variables, l = pk->num_public, n the circuit's domain and w
+ * zk_ntt_fr's root, coeffs = rho_0 .. rho_{V-1} then sigma_0 .. sigma_{n-1}
+ * (n_coeffs = V + n).  rho = rho^pub + rho^priv, rho^pub keeping the entries
+ * i <= l.  For M in {A, B, C} and part in {pub, priv}
+ *   u^{M,part}_j = sum_i M[j][i] rho^part_i  (row j < num_constraints, else 0)
+ *   m^{M,part} = iNTT_n(u^{M,part}), the coefficients of sum_i rho^part_i M_i(x)
+ *   m^M = m^{M,pub} + m^{M,priv}
+ *   T^part = sum_k m^{A,part}_k beta_tau_g1[k] + m^{B,part}_k alpha_tau_g1[k] + m^{C,part}_k tau_g1[k]
+ * Returns ZK_OK whenever a verdict was reached; *status is the first check
+ * that fails, in this order:
+ *   SHAPE     a_len, b_len, b2_len != V, ic_len != V - l - 1, h_len != n,
+ *             vk->ic_len != l + 1, vk->num_public != l, or n_coeffs != V + n
+ *   POINT     a point or array entry of either key fails zk_g1_validate /
+ *             zk_g2_validate (the identity is legal in the arrays: a variable
+ *             absent from a matrix has one); zk_last_error names the array and
+ *             the index.  Not optional: G1's cofactor has small factors, and a
+ *             low-order component survives a random combination with
+ *             noticeable probability
+ *   FIXED     byte for byte (struct padding excluded): pk and vk alpha_g1 against
+ *             alpha_tau_g1[0], pk beta_g1 against beta_tau_g1[0], pk and vk
+ *             beta_g2 against the string's, vk gamma_g2 against the G2 generator,
+ *             vk delta_g2 against pk delta_g2
+ *   DELTA     a delta point is the identity, or e(delta_g1, g2) != e(g1, delta_g2)
+ *   QUERY_A   sum_i rho_i a_g1[i] != sum_k m^A_k tau_g1[k]       (G1 points compared)
+ *   QUERY_B1  sum_i rho_i b_g1[i] != sum_k m^B_k tau_g1[k]
+ *   QUERY_B2  sum_i rho_i b_g2[i] != sum_k m^B_k tau_g2[k]       (G2)
+ *   IC_VK     sum_{i<=l} rho_i vk->ic_g1[i] != T^pub             (gamma = 1)
+ *   IC_PK     e(sum_{i>l} rho_i pk->ic_g1[i-l-1], delta_g2) != e(T^priv, g2)
+ *   H         e(sum_i sigma_i h_g1[i], delta_g2) != e(sum_i sigma_i (tau_g1[i+n] - tau_g1[i]), g2)
+ * The sums over the key are the public 255-bit MSMs; those over the string are
+ * at most six device MSMs over its first n (2n) entries, uploaded once; the
+ * products are the host pairing.  Each coefficient is non-zero and below 2^128,
+ * else ZK_ERR_ARG (after the SHAPE check; zk_last_error names the index), as
+ * in zk_groth16_verify_contribution_sound.  n > N, string arrays shorter than
+ * log_n states and num_public >= num_variables give the codes of
+ * zk_groth16_setup_srs_sound, before any check.
+ * An honest key passes for every delta the chain has reached and every choice
+ * of coefficients; a key with one entry off by a non-zero subgroup element
+ * fails except with probability about 2^-127 over independent uniform
+ * coefficients -- draw them from a cryptographic generator, fresh per call.
+ * What this does NOT establish: that anyone knows the delta shares (the proofs
+ * of knowledge below do that), and that the string itself is well formed -- it
+ * is ASSUMED valid, as for zk_groth16_setup_srs_sound (zk_srs_verify). */
+typedef enum { ZK_KEYSRS_OK = 0, ZK_KEYSRS_SHAPE, ZK_KEYSRS_POINT, ZK_KEYSRS_FIXED, ZK_KEYSRS_DELTA,
+               ZK_KEYSRS_QUERY_A, ZK_KEYSRS_QUERY_B1, ZK_KEYSRS_QUERY_B2, ZK_KEYSRS_IC_VK,
+               ZK_KEYSRS_IC_PK, ZK_KEYSRS_H } zk_key_srs_status;
+int zk_groth16_verify_key_srs_sound(zk_ctx *ctx, const zk_r1cs_csr *qap, const zk_srs *srs,
+                                    const zk_pk *pk, const zk_vk *vk,
+                                    const zk_fr *coeffs, size_t n_coeffs, int *status);
+
 /* ---------------------------------------------- phase-1 contributions --- */
 /* zk_srs_generate's string is known to whoever ran it.  The phase-1 step of a
  * ceremony removes that: each participant multiplies tau, alpha and beta by

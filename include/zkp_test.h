@@ -256,6 +256,15 @@ int zk_test_msm_grouping(zk_ctx *ctx, int which, uint32_t *off_out, uint32_t *ke
  * partial the MSM fails to write cannot pass on the right value an earlier
  * MSM of the same inputs left there.  Waits for the ctx's streams. */
 int zk_test_msm_scrub(zk_ctx *ctx);
+/* The coefficient side of zk_groth16_verify_key_srs_sound on its own
+ * (csrc/keycheck.hip: the split row products, then the six inverse
+ * transforms): out = the six vectors m^{M,part} of that call's description as
+ * 6 n canonical zk_fr, n the circuit's domain -- A pub, A priv, B pub, B priv,
+ * C pub, C priv -- for rho = num_variables canonical values (any values below
+ * r, not only below 2^128; else ZK_ERR_ARG) split at column num_public.
+ * num_public >= num_variables is ZK_ERR_SETUP_PARAMS. */
+int zk_test_key_srs_coeffs(zk_ctx *ctx, const zk_r1cs_csr *qap, uint64_t num_public, const zk_fr *rho,
+                           zk_fr *out);
 
 #ifdef __cplusplus
 }

@@ -69,6 +69,7 @@ EXPORTS = (
     "zk_srs_verify_contribution_proofs",
     "zk_vk_prepare", "zk_vk_dev_free", "zk_vk_dev_bytes", "zk_vk_dev_is_sound", "zk_groth16_prepare_inputs",
     "zk_groth16_verify_many_prepared", "zk_groth16_verify_many_bytes_prepared",
+    "zk_groth16_verify_key_srs_sound",
 )
 # include/zkp_test.h (libzkp_amd_test.so)
 TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fault_after_exchange",
@@ -79,7 +80,7 @@ TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fau
                 "zk_test_g2_mul_scalars_table", "zk_test_split_scalars", "zk_test_field", "zk_test_curve",
                 "zk_test_gn_walk", "zk_test_hash_to_g2_capped", "zk_test_prepared_plan", "zk_test_prepared_run",
                 "zk_test_prepared_force", "zk_test_prepared_info", "zk_test_msm_force", "zk_test_msm_info",
-                "zk_test_msm_grouping", "zk_test_msm_scrub")
+                "zk_test_msm_grouping", "zk_test_msm_scrub", "zk_test_key_srs_coeffs")
 # words of zk_test_msm_info (include/zkp_test.h), and its workspaces beside the five prove slots
 TEST_MSM_INFO = ("c", "nwin", "bits", "sw", "shared", "copies", "nred", "nseg", "segshift", "G", "T", "fix_max",
                  "M", "nbig", "natural_T", "n")
@@ -120,6 +121,9 @@ G1_BYTES, G2_BYTES = 48, 96
 # zk_srs_status: the first check of SRS.verify that fails
 (ZK_SRS_OK, ZK_SRS_SHAPE, ZK_SRS_POINT, ZK_SRS_GENERATOR, ZK_SRS_POWERS_G1, ZK_SRS_POWERS_G2, ZK_SRS_ALPHA,
  ZK_SRS_BETA) = range(8)
+# zk_key_srs_status: the first check of CRS.verify_against_srs that fails
+(ZK_KEYSRS_OK, ZK_KEYSRS_SHAPE, ZK_KEYSRS_POINT, ZK_KEYSRS_FIXED, ZK_KEYSRS_DELTA, ZK_KEYSRS_QUERY_A,
+ ZK_KEYSRS_QUERY_B1, ZK_KEYSRS_QUERY_B2, ZK_KEYSRS_IC_VK, ZK_KEYSRS_IC_PK, ZK_KEYSRS_H) = range(11)
 # zk_srs_contribution_status: the first check of SRS.verify_contribution that fails
 (ZK_SRSC_OK, ZK_SRSC_SHAPE, ZK_SRSC_SHARE, ZK_SRSC_STRING, ZK_SRSC_TAU, ZK_SRSC_ALPHA, ZK_SRSC_BETA) = range(7)
 PROOF_BYTES, PROOF_WORDS = 192, 51
@@ -975,6 +979,21 @@ class Context:
         _check(fn(C.c_void_p(self._h), _p(sc) if len(sc) else None, C.c_size_t(len(sc)), _p(out)), self,
                "zk_test_fixed_base")
         return out[:len(sc)]
+
+    def test_key_srs_coeffs(self, qap, num_public, rho):
+        """zk_test_key_srs_coeffs (test library): the coefficient side of
+        CRS.verify_against_srs on its own -> six lists of n ints, the vectors
+        m^{M,part} for A pub, A priv, B pub, B priv, C pub, C priv, for
+        rho = num_variables values below r split at column num_public."""
+        sc = _fr_rows(rho)
+        if len(sc) != qap.num_variables:
+            raise ValueError("test_key_srs_coeffs: one rho per variable")
+        n = qap.domain_size
+        out = np.zeros((6 * n, 4), dtype=np.uint64)
+        _check(test_lib().zk_test_key_srs_coeffs(C.c_void_p(self._h), C.byref(qap.csr.s), C.c_uint64(num_public),
+                                                 _p(sc), _p(out)), self, "zk_test_key_srs_coeffs")
+        vals = [from_limbs(row) for row in out]
+        return [vals[k * n:(k + 1) * n] for k in range(6)]
 
     def pairing_products(self, g1_points, g2_points, pairs_per_product):
         """zk_pairing_products: product j = prod_{i<k} e(g1[jk+i], g2[jk+i])
@@ -1862,6 +1881,51 @@ class CRS:
             C.byref(after.vk.s), _p(co) if len(co) else None, C.c_size_t(len(co)), C.byref(st))
         _check(rc, ctx, "zk_groth16_verify_contribution_sound")
         return st.value == ZK_CONTRIB_OK, st.value
+
+    def verify_against_srs(self, ctx, srs, coeffs=None):
+        """zk_groth16_verify_key_srs_sound: is this CRS the sound key of its
+        circuit (self.pk.qap) over the string `srs`, for some delta and
+        gamma = 1 -- what from_srs gives, after any number of contribute calls?
+        -> (ok, status), status the first ZK_KEYSRS_* check that fails (SHAPE,
+        POINT, FIXED, DELTA, QUERY_A, QUERY_B1, QUERY_B2, IC_VK, IC_PK, H) or
+        ZK_KEYSRS_OK.  coeffs: num_variables + domain_size non-zero integers
+        below 2^128 (one per variable, then one per h_g1 entry; ints, or their
+        (n, 4) uint64 limbs); None draws them from `secrets`, which is what a
+        real check uses -- a wrong key then passes with probability about
+        2^-127.  No group transform runs:
+        sparse row products, six scalar inverse transforms, MSMs over the key
+        and over the string, a few pairings.  It does not prove that anyone
+        knows the delta shares, and it takes the string as valid (SRS.verify).
+        SetupError for reference-mode keys, ValueError for a bad coefficient,
+        DomainTooSmall when the circuit's domain exceeds the string's."""
+        if not (self.pk.sound and self.vk.sound):
+            raise SetupError("verify_against_srs: sound keys only")
+        qap = self.pk.qap
+        n = qap.num_variables + qap.domain_size
+        if coeffs is None:
+            import secrets
+            co = np.zeros((n, 4), dtype=np.uint64)      # uniform on [1, 2^128): zero rows are drawn again
+            todo = np.arange(n)
+            while len(todo):
+                co[todo, :2] = np.frombuffer(secrets.token_bytes(16 * len(todo)), dtype=np.uint64).reshape(-1, 2)
+                todo = todo[(co[todo, 0] | co[todo, 1]) == 0]
+        elif isinstance(coeffs, np.ndarray):                # (n, 4) canonical limbs, as fr_array gives
+            co = _fr_rows(coeffs)
+        else:
+            coeffs = [int(c) for c in coeffs]
+            for i, c in enumerate(coeffs):
+                if not 0 <= c < R:
+                    raise ValueError(f"verify_against_srs: coefficient {i} must be non-zero and below 2^128")
+            co = _fr_rows(coeffs) if len(coeffs) else np.zeros((0, 4), dtype=np.uint64)
+        bad = np.flatnonzero(((co[:, 0] | co[:, 1]) == 0) | ((co[:, 2] | co[:, 3]) != 0))
+        if len(bad):
+            raise ValueError(f"verify_against_srs: coefficient {bad[0]} must be non-zero and below 2^128")
+        st = C.c_int(-1)
+        rc = lib().zk_groth16_verify_key_srs_sound(
+            C.c_void_p(ctx._h), C.byref(qap.csr.s), C.byref(srs._bind()), C.byref(self.pk._bind()),
+            C.byref(self.vk.s), _p(co) if len(co) else None, C.c_size_t(len(co)), C.byref(st))
+        _check(rc, ctx, "zk_groth16_verify_key_srs_sound")
+        return st.value == ZK_KEYSRS_OK, st.value
 
     # ---- phase-2 contributions with a proof of knowledge ----
     def digest(self):

@@ -318,7 +318,7 @@ void gntt_device(zk_ctx* ctx, const uint64_t* d_abi, uint32_t log_n, bool invers
 }
 
 // host array <-> device, in pieces of ctx->point_chunk points
-static void chunked_copy(zk_ctx* ctx, void* dst, const void* src, size_t n, size_t sz, hipMemcpyKind kind) {
+void chunked_copy(zk_ctx* ctx, void* dst, const void* src, size_t n, size_t sz, hipMemcpyKind kind) {
   const size_t chunk = std::max<size_t>(ctx->point_chunk, 1);
   for (size_t lo = 0; lo < n; lo += chunk) {
     const size_t m = std::min(chunk, n - lo);
@@ -409,16 +409,16 @@ static void colsum_points(zk_ctx* ctx, uint64_t V, const std::vector<uint64_t>& 
   affine_to_host<F>(ctx, d_aff.as<A>(), V, host_out);   // synchronises: the host vectors and buffers die after it
 }
 
-static bool same_g1(const zk_g1_affine& a, const zk_g1_affine& b) {
+bool same_g1(const zk_g1_affine& a, const zk_g1_affine& b) {
   return !std::memcmp(a.x, b.x, 48) && !std::memcmp(a.y, b.y, 48) && a.infinity == b.infinity;
 }
-static bool same_g2(const zk_g2_affine& a, const zk_g2_affine& b) {
+bool same_g2(const zk_g2_affine& a, const zk_g2_affine& b) {
   return !std::memcmp(a.x, b.x, 96) && !std::memcmp(a.y, b.y, 96) && a.infinity == b.infinity;
 }
 static bool fr_is0(const zk_fr& a) { return (a.l[0] | a.l[1] | a.l[2] | a.l[3]) == 0; }
 
 // the generators as ABI points, through the fixed-base kernel
-static void generators(zk_ctx* ctx, zk_g1_affine& g1, zk_g2_affine& g2) {
+void generators(zk_ctx* ctx, zk_g1_affine& g1, zk_g2_affine& g2) {
   const zk_fr one = {{1, 0, 0, 0}};
   std::memset(&g1, 0, sizeof g1);
   std::memset(&g2, 0, sizeof g2);
@@ -620,7 +620,7 @@ static bool negated_g1(const zk_g1_affine& p, zk_g1_affine& out) {
   return true;
 }
 // e(a, p) == e(b, q)
-static bool pairs_equal(const zk_g1_affine& a, const zk_g2_affine& p, const zk_g1_affine& b, const zk_g2_affine& q) {
+bool pairs_equal(const zk_g1_affine& a, const zk_g2_affine& p, const zk_g1_affine& b, const zk_g2_affine& q) {
   zk_g1_affine g1[2];
   zk_g2_affine g2[2] = {p, q};
   int one = 0;

@@ -178,4 +178,14 @@ template <class F>
 void gntt_device(zk_ctx* ctx, const uint64_t* d_abi, uint32_t log_n, bool inverse,
                  Affine<typename GnField<F>::Raw>* d_out, const char* phase);
 
+// Shared with keycheck.hip: n elements of sz bytes between host and device in
+// pieces of ctx->point_chunk (not synchronised); a point's words without the
+// struct padding; the generators as ABI points; e(a, p) == e(b, q) through the
+// host pairing.
+void chunked_copy(zk_ctx* ctx, void* dst, const void* src, size_t n, size_t sz, hipMemcpyKind kind);
+bool same_g1(const zk_g1_affine& a, const zk_g1_affine& b);
+bool same_g2(const zk_g2_affine& a, const zk_g2_affine& b);
+void generators(zk_ctx* ctx, zk_g1_affine& g1, zk_g2_affine& g2);
+bool pairs_equal(const zk_g1_affine& a, const zk_g2_affine& p, const zk_g1_affine& b, const zk_g2_affine& q);
+
 }  // namespace zk

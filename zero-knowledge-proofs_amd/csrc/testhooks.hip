@@ -9,6 +9,7 @@
 #include "ceremony.hpp"
 #include "ctx.hpp"
 #include "hash.hpp"
+#include "keycheck.hpp"
 #include "msm.hpp"
 #include "mulvec.hpp"
 #include "pairing.hpp"
@@ -944,4 +945,10 @@ int zk_test_msm_scrub(zk_ctx* ctx) {
     ZK_HIP(hipDeviceSynchronize());
     return ZK_OK;
   })
+}
+
+// ---- the coefficient side of zk_groth16_verify_key_srs_sound on its own ----
+int zk_test_key_srs_coeffs(zk_ctx* ctx, const zk_r1cs_csr* qap, uint64_t num_public, const zk_fr* rho, zk_fr* out) {
+  if (!ctx || !qap || !rho || !out) return ZK_ERR_ARG;
+  ZK_TGUARD(ctx, { return key_srs_coeffs_host(ctx, qap, num_public, rho, out); })
 }

@@ -856,6 +856,89 @@ typedef enum { ZK_SRS_OK = 0, ZK_SRS_SHAPE, ZK_SRS_POINT, ZK_SRS_GENERATOR, ZK_S
                ZK_SRS_POWERS_G2, ZK_SRS_ALPHA, ZK_SRS_BETA } zk_srs_status;
 int zk_srs_verify(zk_ctx *ctx, const zk_srs *srs, const zk_fr *coeffs, size_t n_coeffs, int *status);
 
+/* ------------------------------------------- prepared powers-of-tau strings --- */
+/* The inverse group transforms of zk_groth16_setup_srs_sound depend on the
+ * string and the domain size only, and they are nearly all of its time.  A
+ * PREPARED string is their result for one n = 2^log_n, resident on the device:
+ * [L_i]_1, [alpha L_i]_1, [beta L_i]_1 back to back, [L_i]_2 and
+ * h[i] = tau_g1[i + n] - tau_g1[i], n * (3 * 96 + 192 + 96) bytes
+ * (zk_srs_dev_bytes), beside alpha_tau_g1[0], beta_tau_g1[0] and beta_g2.
+ * Prepare once, then make the key of any number of circuits of that size.  No
+ * reference counterpart.
+ *
+ * zk_srs_prepare: log_n above the string's, or arrays shorter than the
+ * string's log_n states -> ZK_ERR_DOMAIN; tau_g1[n] == tau_g1[0] ->
+ * ZK_ERR_SETUP_PARAMS with the sound setup's message; a failed allocation ->
+ * ZK_ERR_DEVICE.  The string is ASSUMED valid (zk_srs_verify).  On any error
+ * *out is untouched.  The handle belongs to ctx's device and is read-only
+ * after this call. */
+typedef struct zk_srs_dev zk_srs_dev;
+int  zk_srs_prepare(zk_ctx *ctx, const zk_srs *srs, uint32_t log_n, zk_srs_dev **out);
+void zk_srs_dev_free(zk_srs_dev *p);
+int  zk_srs_dev_log_n(const zk_srs_dev *p, uint32_t *log_n);
+int  zk_srs_dev_bytes(const zk_srs_dev *p, uint64_t *bytes);
+/* The prepared form on the host, n = 2^log_n entries per array
+ * (caller-allocated, len >= n): l_g1[i] = [L_i(tau)]_1, alpha_l_g1, beta_l_g1
+ * and l_g2 likewise, h_g1[i] = [tau^i (tau^n - 1)]_1; alpha_g1, beta_g1 and
+ * beta_g2 the string's.  Export writes canonical points in pieces of
+ * ZK_OPT_POINT_CHUNK and sets log_n and the three points (len < n or a NULL
+ * array -> ZK_ERR_ARG).  Import checks the SHAPE only (len >= n, log_n <= 31
+ * else ZK_ERR_DOMAIN, non-NULL arrays): whether the points are what they claim
+ * is zk_srs_lagrange_verify's job.  Export then import gives a handle whose
+ * keys are identical.  OUT OF SCOPE: a file format for either form. */
+typedef struct {
+  uint32_t log_n;
+  zk_g1_affine *l_g1, *alpha_l_g1, *beta_l_g1, *h_g1;
+  zk_g2_affine *l_g2;
+  uint64_t len;                                     /* entries allocated in each array */
+  zk_g1_affine alpha_g1, beta_g1;
+  zk_g2_affine beta_g2;
+} zk_srs_lagrange;
+int zk_srs_dev_export(zk_ctx *ctx, const zk_srs_dev *p, zk_srs_lagrange *out);
+int zk_srs_dev_import(zk_ctx *ctx, const zk_srs_lagrange *lag, zk_srs_dev **out);
+/* Is lag the prepared form of srs at lag->log_n?  No transform of points runs:
+ * with rho = coeffs (n of them) and c the inverse zk_ntt_fr transform of rho,
+ * [L_i(tau)] = (1/n) sum_k w^(-ik) [tau^k] gives sum_i rho_i [L_i] =
+ * sum_k c_k [tau^k], two MSMs whose results are points of one group and are
+ * compared as affine words.  Returns ZK_OK whenever a verdict was reached;
+ * *status is the first check that fails:
+ *   SHAPE        lag->len < n, lag->log_n above the string's (or the string's
+ *                arrays shorter than its log_n states), or n_coeffs != n
+ *   POINT        an entry of the five arrays or one of the three points fails
+ *                zk_g1_validate / zk_g2_validate or is the identity;
+ *                zk_last_error names the array and the index
+ *   FIXED        alpha_g1, beta_g1 or beta_g2 differ from alpha_tau_g1[0],
+ *                beta_tau_g1[0], beta_g2 of the string
+ *   LAGRANGE_G1  sum rho_i l_g1[i] != sum c_k tau_g1[k]
+ *   ALPHA        the same over alpha_l_g1 / alpha_tau_g1
+ *   BETA         the same over beta_l_g1 / beta_tau_g1
+ *   LAGRANGE_G2  the same over l_g2 / tau_g2
+ *   H            h_g1 is not the recomputed differences, byte for byte
+ * Each coefficient is non-zero and below 2^128, else ZK_ERR_ARG (after the
+ * SHAPE check).  The rho side runs as 128-bit, the c side as 255-bit public
+ * MSMs.  Every point was shown to lie in the prime-order subgroup first, so a
+ * wrong entry survives with probability about 2^-128 over independent uniform
+ * coefficients.  The string is ASSUMED valid (zk_srs_verify). */
+typedef enum { ZK_LAG_OK = 0, ZK_LAG_SHAPE, ZK_LAG_POINT, ZK_LAG_FIXED, ZK_LAG_LAGRANGE_G1, ZK_LAG_ALPHA,
+               ZK_LAG_BETA, ZK_LAG_LAGRANGE_G2, ZK_LAG_H } zk_srs_lagrange_status;
+int zk_srs_lagrange_verify(zk_ctx *ctx, const zk_srs *srs, const zk_srs_lagrange *lag,
+                           const zk_fr *coeffs, size_t n_coeffs, int *status);
+/* The key of zk_groth16_setup_srs_sound from a prepared string, byte for byte:
+ * the column sums over the handle's points, the generators, h_g1 copied.  A
+ * Lagrange basis belongs to one size: a circuit whose padded domain is not
+ * exactly the handle's 2^log_n -> ZK_ERR_DOMAIN (zk_last_error names both).
+ * Other errors as zk_groth16_setup_srs_sound; on any error the outputs are
+ * untouched.  The handle is only read: any number of calls may follow. */
+int zk_groth16_setup_prepared_sound(zk_ctx *ctx, const zk_r1cs_csr *qap, const zk_srs_dev *p,
+                                    uint64_t num_public, zk_pk *pk, zk_vk *vk /* may be NULL */);
+/* The same key straight into a device key (unsharded), without a host key:
+ * what zk_pk_upload_sound makes of zk_groth16_setup_prepared_sound's pk --
+ * the same zk_pk_device_bytes, the same proofs.  ZK_OPT_SOUND_WIN_C and
+ * ZK_OPT_SOUND_COPIES apply as for zk_groth16_setup_sound_dev.  vk, when
+ * given, is filled as above. */
+int zk_groth16_setup_prepared_sound_dev(zk_ctx *ctx, const zk_r1cs_csr *qap, const zk_srs_dev *p,
+                                        uint64_t num_public, zk_pk_dev **pk_out, zk_vk *vk /* may be NULL */);
+
 /* ------------------------------------------------ a key against its string --- */
 /* Is (pk, vk) the sound key of the circuit qap over the string srs, for SOME
  * delta and gamma = 1 (what zk_groth16_setup_srs_sound makes, after any number

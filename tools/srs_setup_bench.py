@@ -30,6 +30,27 @@ string of exactly that size from known secrets:
             a CPU implementation.
 
   python tools/srs_setup_bench.py [--log-n 16 20] [--out profiles/srs_setup_bench.json]
+
+--prepared measures the prepared strings instead (zk_srs_prepare and what reads
+its handle), in one process per size, every call in turn within one iteration
+and the order reversed every other iteration, median of --runs wall times after
+--warmup:
+
+  prepare               SRS.prepare (the four inverse transforms and the H
+                        differences, kept on the device)
+  from_prepared         CRS.from_prepared, a host key
+  from_prepared_device  CRS.from_prepared_device, a device key
+  from_srs              CRS.from_srs, the host key from the monomial string
+  from_srs_upload       CRS.from_srs and DeviceProvingKey.upload of its key
+  lagrange_verify       LagrangeSRS.verify of the exported handle, drawn coefficients
+  phases                one profiled call of each (zk_ctx_profile); srs_csc_host is
+                        the host's CSC builds; prepared_* and lag_* are host wall
+                        times too, each ending in a synchronise (the key's download
+                        and the copy into the caller's arrays; the device key's
+                        matrices, its slots and pk_finish; the check's validation
+                        and its MSMs over either form)
+
+  python tools/srs_setup_bench.py --prepared [--log-n 16 20] [--out profiles/srs_prepared_bench.json]
 """
 import argparse
 import importlib
@@ -51,6 +72,93 @@ from contribute_bench import host_mul_ms, stats  # noqa: E402
 PHASES = ("srs_ntt_g1_tau", "srs_ntt_g1_alpha", "srs_ntt_g1_beta", "srs_ntt_g2", "srs_colsum_a_g1", "srs_colsum_b_g1",
           "srs_colsum_b_g2", "srs_colsum_ic", "srs_hdiff")
 PK_ARRAYS = ("a_g1", "b_g1", "b_g2", "ic_g1", "h_g1")
+COLSUMS = ("srs_csc_host", "srs_colsum_a_g1", "srs_colsum_b_g1", "srs_colsum_b_g2", "srs_colsum_ic")
+HOST_KEY = COLSUMS + ("prepared_download", "prepared_fill_host")
+DEV_KEY = COLSUMS + ("prepared_dev_create", "prepared_dev_fill", "prepared_dev_finish")
+LAG_PHASES = ("lag_validate", "lag_scalars", "lag_msm_lagrange", "lag_msm_srs", "srs_hdiff")
+
+
+def prepared(args, zkp, pyref, bid):
+    rng = pyref.SplitMix64(0x5255)
+    tau, alpha, beta = rng.fr(), rng.fr(), rng.fr()
+    res = {"build": bid, "circuit": "synthetic n x (x*y=z), num_public 1, sound keys, gamma = delta = 1",
+           "method": "one process per record, one ctx; wall ms, median of %d after %d warm-up, the calls in turn "
+                     "and the order reversed every other iteration" % (args.runs, args.warmup)}
+    if os.path.exists(args.out):           # sizes measured by earlier calls stay
+        with open(args.out) as f:
+            old = json.load(f)
+        if old.get("build") == bid:
+            res = old
+    with zkp.Context(0) as ctx:
+        def profiled(fn, names):
+            ctx.profile(0)
+            ctx.profile(1)
+            out = fn()
+            prof = ctx.profile_read()
+            ctx.profile(0)
+            return out, {nm: prof[nm]["ms"] for nm in names if nm in prof}
+
+        for log_n in args.log_n:
+            n = 1 << log_n
+            qap = zkp.QAP(zkp.CSRMatrices.synthetic(n))
+            srs = zkp.SRS.generate(ctx, log_n, tau, alpha, beta)
+            prep = srs.prepare(ctx)
+            lag = prep.export()
+            row = {"constraints": n, "prepared_device_bytes": prep.device_bytes}
+            keep = {}
+
+            def do_prepare():
+                srs.prepare(ctx).free()
+
+            def do_host():
+                keep["prepared"] = zkp.CRS.from_prepared(ctx, qap, prep, 1)
+
+            def do_device():
+                zkp.CRS.from_prepared_device(ctx, qap, prep, 1).free()
+
+            def do_srs():
+                keep["srs"] = zkp.CRS.from_srs(ctx, qap, srs, 1)
+
+            def do_srs_upload():
+                zkp.DeviceProvingKey.upload(ctx, zkp.CRS.from_srs(ctx, qap, srs, 1).pk).free()
+
+            def do_verify():
+                if lag.verify(ctx, srs) != (True, zkp.ZK_LAG_OK):
+                    raise SystemExit("the exported handle fails LagrangeSRS.verify")
+
+            calls = (("prepare", do_prepare), ("from_prepared", do_host), ("from_prepared_device", do_device),
+                     ("from_srs", do_srs), ("from_srs_upload", do_srs_upload), ("lagrange_verify", do_verify))
+            ts = {name: [] for name, _ in calls}
+            for it in range(args.warmup + args.runs):
+                for name, fn in (calls if it % 2 == 0 else calls[::-1]):
+                    t0 = time.perf_counter()
+                    fn()
+                    if it >= args.warmup:
+                        ts[name].append((time.perf_counter() - t0) * 1e3)
+            for nm in PK_ARRAYS:
+                if not np.array_equal(getattr(keep["prepared"].pk, nm), getattr(keep["srs"].pk, nm)):
+                    raise SystemExit("the key from the prepared string differs from from_srs's in " + nm)
+            keep.clear()
+            for name, _ in calls:
+                row[name] = stats(ts[name])
+            for name in ("from_prepared", "from_prepared_device"):
+                row["from_srs_over_" + name] = row["from_srs"]["median_ms"] / row[name]["median_ms"]
+            row["phases_ms"] = {
+                "prepare": profiled(do_prepare, PHASES)[1],
+                "from_prepared": profiled(do_host, HOST_KEY)[1],
+                "from_prepared_device": profiled(do_device, DEV_KEY)[1],
+                "from_srs": profiled(do_srs, PHASES + COLSUMS[:1])[1],
+                "lagrange_verify": profiled(do_verify, LAG_PHASES)[1],
+            }
+            keep.clear()
+            print("2^%d prepared" % log_n, json.dumps(row), flush=True)
+            res["2p%d" % log_n] = row
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(res, f, indent=1, sort_keys=True)
+                f.write("\n")
+            prep.free()
+            del srs, lag
 
 
 def main():
@@ -59,14 +167,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--srs-runs", type=int, nargs="+", default=[0, 64, 256, 1024, 4096])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "srs_setup_bench.json"))
+    ap.add_argument("--prepared", action="store_true", help="measure the prepared strings instead")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.runs < 3:
         ap.error("--runs must be at least 3")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "srs_prepared_bench.json" if args.prepared else "srs_setup_bench.json")
 
     zkp = importlib.import_module("zero-knowledge-proofs_amd")
     import pyref
     bid = zkp.check_build()
+    if args.prepared:
+        return prepared(args, zkp, pyref, bid)
     rng = pyref.SplitMix64(0x5255)
     tau, alpha, beta = rng.fr(), rng.fr(), rng.fr()
     params = zkp.SetupParams(alpha, beta, 1, 1, tau)

@@ -70,6 +70,9 @@ EXPORTS = (
     "zk_vk_prepare", "zk_vk_dev_free", "zk_vk_dev_bytes", "zk_vk_dev_is_sound", "zk_groth16_prepare_inputs",
     "zk_groth16_verify_many_prepared", "zk_groth16_verify_many_bytes_prepared",
     "zk_groth16_verify_key_srs_sound",
+    "zk_srs_prepare", "zk_srs_dev_free", "zk_srs_dev_log_n", "zk_srs_dev_bytes", "zk_srs_dev_export",
+    "zk_srs_dev_import", "zk_srs_lagrange_verify", "zk_groth16_setup_prepared_sound",
+    "zk_groth16_setup_prepared_sound_dev",
 )
 # include/zkp_test.h (libzkp_amd_test.so)
 TEST_EXPORTS = ("zk_test_prove_virtual_shards", "zk_test_exchange", "zk_test_fault_after_exchange",
@@ -121,6 +124,9 @@ G1_BYTES, G2_BYTES = 48, 96
 # zk_srs_status: the first check of SRS.verify that fails
 (ZK_SRS_OK, ZK_SRS_SHAPE, ZK_SRS_POINT, ZK_SRS_GENERATOR, ZK_SRS_POWERS_G1, ZK_SRS_POWERS_G2, ZK_SRS_ALPHA,
  ZK_SRS_BETA) = range(8)
+# zk_srs_lagrange_status: the first check of LagrangeSRS.verify that fails
+(ZK_LAG_OK, ZK_LAG_SHAPE, ZK_LAG_POINT, ZK_LAG_FIXED, ZK_LAG_LAGRANGE_G1, ZK_LAG_ALPHA, ZK_LAG_BETA,
+ ZK_LAG_LAGRANGE_G2, ZK_LAG_H) = range(9)
 # zk_key_srs_status: the first check of CRS.verify_against_srs that fails
 (ZK_KEYSRS_OK, ZK_KEYSRS_SHAPE, ZK_KEYSRS_POINT, ZK_KEYSRS_FIXED, ZK_KEYSRS_DELTA, ZK_KEYSRS_QUERY_A,
  ZK_KEYSRS_QUERY_B1, ZK_KEYSRS_QUERY_B2, ZK_KEYSRS_IC_VK, ZK_KEYSRS_IC_PK, ZK_KEYSRS_H) = range(11)
@@ -247,6 +253,13 @@ class _SRS(C.Structure):
                 ("beta_g2", _G2)]
 
 
+class _SRSLagrange(C.Structure):
+    _fields_ = [("log_n", C.c_uint32),
+                ("l_g1", C.c_void_p), ("alpha_l_g1", C.c_void_p), ("beta_l_g1", C.c_void_p), ("h_g1", C.c_void_p),
+                ("l_g2", C.c_void_p), ("len", C.c_uint64),
+                ("alpha_g1", _G1), ("beta_g1", _G1), ("beta_g2", _G2)]
+
+
 class _SRSShare(C.Structure):
     _fields_ = [("tau_g2", _G2), ("alpha_g2", _G2), ("beta_g2", _G2)]
 
@@ -292,13 +305,17 @@ def lib():
                     continue
                 raise ImportError(f"{LIB_PATH} does not export {name}")
             if name not in ("zk_ctx_create", "zk_ctx_destroy", "zk_last_error",
-                            "zk_msm_bases_free", "zk_pk_free", "zk_build_id", "zk_vk_dev_free"):
+                            "zk_msm_bases_free", "zk_pk_free", "zk_build_id", "zk_vk_dev_free",
+                            "zk_srs_dev_free"):
                 f.restype = C.c_int
         L.zk_msm_bases_free.argtypes = [C.c_void_p]
         L.zk_pk_free.argtypes = [C.c_void_p]
         if hasattr(L, "zk_vk_dev_free"):
             L.zk_vk_dev_free.restype = None
             L.zk_vk_dev_free.argtypes = [C.c_void_p]
+        if hasattr(L, "zk_srs_dev_free"):
+            L.zk_srs_dev_free.restype = None
+            L.zk_srs_dev_free.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -1816,6 +1833,38 @@ class CRS:
         _check(rc, ctx, "zk_groth16_setup_srs_sound")
         return cls(pk, vk)
 
+    @classmethod
+    def from_prepared(cls, ctx, qap, prepared, num_public):
+        """zk_groth16_setup_prepared_sound: from_srs's CRS, byte for byte, from
+        a PreparedSRS (SRS.prepare) -- the column sums only, the transforms were
+        paid once.  DomainTooSmall unless the circuit's domain is exactly the
+        prepared one; SetupError for num_public >= num_variables."""
+        if num_public >= qap.num_variables:
+            raise SetupError("Number of public inputs must be less than total variables")
+        pk = ProvingKey(qap.num_variables, qap.domain_size, num_public, qap, True)
+        vk = VerificationKey(num_public, True)
+        rc = lib().zk_groth16_setup_prepared_sound(C.c_void_p(ctx._h), C.byref(qap.csr.s), C.c_void_p(prepared._h),
+                                                   C.c_uint64(num_public), C.byref(pk._bind()), C.byref(vk.s))
+        _check(rc, ctx, "zk_groth16_setup_prepared_sound")
+        return cls(pk, vk)
+
+    @staticmethod
+    def from_prepared_device(ctx, qap, prepared, num_public, vk=None):
+        """zk_groth16_setup_prepared_sound_dev: from_prepared's proving key
+        straight into HBM, no host key in between -> DeviceProvingKey, the one
+        DeviceProvingKey.upload makes of from_prepared(...).pk.  vk: a
+        VerificationKey(num_public, sound=True) to fill beside it."""
+        if num_public >= qap.num_variables:
+            raise SetupError("Number of public inputs must be less than total variables")
+        if vk is not None and (vk.num_public != num_public or not vk.sound):
+            raise ValueError("from_prepared_device: vk needs the call's num_public and sound mode")
+        h = C.c_void_p()
+        rc = lib().zk_groth16_setup_prepared_sound_dev(C.c_void_p(ctx._h), C.byref(qap.csr.s),
+                                                       C.c_void_p(prepared._h), C.c_uint64(num_public), C.byref(h),
+                                                       C.byref(vk.s) if vk is not None else None)
+        _check(rc, ctx, "zk_groth16_setup_prepared_sound_dev")
+        return DeviceProvingKey(ctx, h.value, qap)
+
     # ---- phase-2 contributions (sound keys) ----
     def copy(self):
         """A CRS with arrays and points of its own."""
@@ -2166,6 +2215,149 @@ class SRS:
                                                      _p(pr) if m else None, C.c_size_t(m), _p(st) if m else None)
         _check(rc, ctx, "zk_srs_verify_contribution_proofs")
         return st
+
+    # ---- prepared strings ----
+    def prepare(self, ctx, log_n=None):
+        """zk_srs_prepare: the Lagrange form of this string for the domain
+        2^log_n (default: the string's own), resident on the device -> a
+        PreparedSRS.  The four inverse group transforms run here, once;
+        CRS.from_prepared / from_prepared_device then make the key of any
+        circuit of that size from column sums alone.  DomainTooSmall for a
+        log_n above the string's, SetupError for tau on that domain."""
+        log_n = self.log_n if log_n is None else int(log_n)
+        if not 0 <= log_n <= 31:
+            raise DomainTooSmall(f"a domain of 2^{log_n} does not exist (log_n in [0, 31])")
+        h = C.c_void_p()
+        _check(lib().zk_srs_prepare(C.c_void_p(ctx._h), C.byref(self._bind()), C.c_uint32(log_n), C.byref(h)), ctx,
+               "zk_srs_prepare")
+        return PreparedSRS(ctx, h.value)
+
+
+class PreparedSRS:
+    """A prepared powers-of-tau string in HBM (zk_srs_dev): [L_i]_1,
+    [alpha L_i]_1, [beta L_i]_1, [L_i]_2 and the h_g1 differences for ONE
+    domain size, read-only.  From SRS.prepare or LagrangeSRS.upload."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self._h = ctx, handle
+
+    @property
+    def log_n(self):
+        v = C.c_uint32()
+        _check(lib().zk_srs_dev_log_n(C.c_void_p(self._h), C.byref(v)), None, "zk_srs_dev_log_n")
+        return v.value
+
+    @property
+    def domain_size(self):
+        return 1 << self.log_n
+
+    @property
+    def device_bytes(self):
+        """zk_srs_dev_bytes: device memory the handle holds."""
+        v = C.c_uint64()
+        _check(lib().zk_srs_dev_bytes(C.c_void_p(self._h), C.byref(v)), None, "zk_srs_dev_bytes")
+        return v.value
+
+    def export(self):
+        """zk_srs_dev_export -> a LagrangeSRS of canonical host points."""
+        lag = LagrangeSRS(self.log_n)
+        s = lag._bind()
+        _check(lib().zk_srs_dev_export(C.c_void_p(self.ctx._h), C.c_void_p(self._h), C.byref(s)), self.ctx,
+               "zk_srs_dev_export")
+        for nm in ("alpha_g1", "beta_g1", "beta_g2"):
+            setattr(lag, nm, np.array(getattr(s, nm).w, dtype=np.uint64))
+        return lag
+
+    def free(self):
+        if getattr(self, "_h", None):
+            lib().zk_srs_dev_free(C.c_void_p(self._h))
+            self._h = None
+
+    def __del__(self):
+        self.free()
+
+
+class LagrangeSRS:
+    """A prepared string on the host (zk_srs_lagrange), n = 2^log_n entries per
+    array: l_g1, alpha_l_g1, beta_l_g1, h_g1 (n, 13) and l_g2 (n, 25) words,
+    alpha_g1, beta_g1 (13) and beta_g2 (25).  upload() takes it as it is;
+    verify() is what tells whether it belongs to a string."""
+
+    _ARRAYS = ("l_g1", "alpha_l_g1", "beta_l_g1", "h_g1", "l_g2")
+
+    def __init__(self, log_n):
+        self.log_n = int(log_n)
+        if not 0 <= self.log_n <= 31:
+            raise DomainTooSmall(f"a domain of 2^{self.log_n} does not exist (log_n in [0, 31])")
+        n = 1 << self.log_n
+        for nm in self._ARRAYS:
+            setattr(self, nm, np.zeros((n, G2_WORDS if nm == "l_g2" else G1_WORDS), dtype=np.uint64))
+        self.alpha_g1 = np.zeros(G1_WORDS, dtype=np.uint64)
+        self.beta_g1 = np.zeros(G1_WORDS, dtype=np.uint64)
+        self.beta_g2 = np.zeros(G2_WORDS, dtype=np.uint64)
+        self.s = _SRSLagrange()
+
+    def _bind(self):
+        s = self.s
+        s.log_n = self.log_n
+        ln = None
+        for nm in self._ARRAYS:
+            a = getattr(self, nm)
+            if not (isinstance(a, np.ndarray) and a.dtype == np.uint64 and a.flags.c_contiguous):
+                a = np.ascontiguousarray(a, dtype=np.uint64)
+                setattr(self, nm, a)
+            setattr(s, nm, a.ctypes.data)
+            ln = len(a) if ln is None else min(ln, len(a))
+        s.len = ln
+        for nm in ("alpha_g1", "beta_g1", "beta_g2"):
+            f = getattr(s, nm)
+            for i, w in enumerate(np.asarray(getattr(self, nm), dtype=np.uint64).reshape(-1)):
+                f.w[i] = int(w)
+        return s
+
+    def copy(self):
+        """A prepared string with arrays of its own."""
+        new = LagrangeSRS(self.log_n)
+        for nm in self._ARRAYS + ("alpha_g1", "beta_g1", "beta_g2"):
+            setattr(new, nm, np.array(getattr(self, nm), dtype=np.uint64, copy=True))
+        return new
+
+    def upload(self, ctx):
+        """zk_srs_dev_import -> a PreparedSRS.  Only the shape is checked."""
+        h = C.c_void_p()
+        _check(lib().zk_srs_dev_import(C.c_void_p(ctx._h), C.byref(self._bind()), C.byref(h)), ctx,
+               "zk_srs_dev_import")
+        return PreparedSRS(ctx, h.value)
+
+    def verify(self, ctx, srs, coeffs=None):
+        """zk_srs_lagrange_verify: is this the prepared form of `srs` at this
+        log_n? -> (ok, status), status the first ZK_LAG_* check that fails
+        (SHAPE, POINT, FIXED, LAGRANGE_G1, ALPHA, BETA, LAGRANGE_G2, H) or
+        ZK_LAG_OK.  coeffs: 2^log_n non-zero integers below 2^128; None draws
+        them from `secrets`, which is what a real check uses -- a wrong entry
+        then passes with probability about 2^-128.  No group transform runs:
+        one scalar inverse transform and eight MSMs.  It takes the string as
+        valid (SRS.verify).  ValueError for a bad coefficient or count."""
+        n = 1 << self.log_n
+        if coeffs is None:
+            import secrets
+            co = np.zeros((n, 4), dtype=np.uint64)      # uniform on [1, 2^128): zero rows are drawn again
+            todo = np.arange(n)
+            while len(todo):
+                co[todo, :2] = np.frombuffer(secrets.token_bytes(16 * len(todo)), dtype=np.uint64).reshape(-1, 2)
+                todo = todo[(co[todo, 0] | co[todo, 1]) == 0]
+        else:
+            coeffs = [int(c) for c in coeffs]
+            if len(coeffs) != n:
+                raise ValueError(f"LagrangeSRS.verify: {n} coefficients, one per entry")
+            if any(not 0 < c < (1 << 128) for c in coeffs):
+                raise ValueError("LagrangeSRS.verify: every coefficient must be non-zero and below 2^128")
+            co = _fr_rows(coeffs)
+        st = C.c_int(-1)
+        rc = lib().zk_srs_lagrange_verify(C.c_void_p(ctx._h), C.byref(srs._bind()), C.byref(self._bind()), _p(co),
+                                          C.c_size_t(len(co)), C.byref(st))
+        _check(rc, ctx, "zk_srs_lagrange_verify")
+        return st.value == ZK_LAG_OK, st.value
 
 
 # -------------------------------------------------------------- prove ----

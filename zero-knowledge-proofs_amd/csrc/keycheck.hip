@@ -14,7 +14,6 @@
 //   [alpha_tau_g1[0, n) | beta_tau_g1[0, n) | tau_g1[0, 2n)]
 // so that every G1 sum is an MSM over a contiguous range of it.  The MSMs, the
 // transforms, the point validation and the host pairing are the library's own.
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -153,17 +152,6 @@ int key_srs_coeffs_host(zk_ctx* ctx, const zk_r1cs_csr* q, uint64_t num_public, 
 }
 
 // ------------------------------------------------------------- helpers ---
-// wall time of a host-side phase into the profiler
-struct HostPhase {
-  Prof& prof;
-  const char* name;
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  HostPhase(Prof& p, const char* nm) : prof(p), name(nm) {}
-  ~HostPhase() {
-    prof.add_host(name, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  }
-};
-
 // One array of the key through the point validation (the identity is legal: a
 // variable absent from a matrix has one).  true when every entry is valid; rc:
 // ZK_OK or the call's own failure.  names: one per entry, else name[index].

@@ -20,6 +20,7 @@
 // The array is normalised once at the end (batch_normalize).
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <vector>
 
 #include "host_pairing.hpp"
@@ -329,7 +330,7 @@ void chunked_copy(zk_ctx* ctx, void* dst, const void* src, size_t n, size_t sz, 
 
 // n device affine points -> canonical ABI words in host memory
 template <class F>
-static void affine_to_host(zk_ctx* ctx, const Affine<typename GnField<F>::Raw>* d_in, size_t n, void* host_out) {
+void affine_to_host(zk_ctx* ctx, const Affine<typename GnField<F>::Raw>* d_in, size_t n, void* host_out) {
   if (!n) return;
   constexpr size_t SZ = 8 * GnField<F>::W;
   DevBuf w;
@@ -339,6 +340,8 @@ static void affine_to_host(zk_ctx* ctx, const Affine<typename GnField<F>::Raw>* 
   chunked_copy(ctx, host_out, w.p, n, SZ, hipMemcpyDeviceToHost);
   ZK_HIP(hipStreamSynchronize(ctx->stream));
 }
+template void affine_to_host<FqC>(zk_ctx*, const G1A*, size_t, void*);
+template void affine_to_host<Fq2C>(zk_ctx*, const G2A*, size_t, void*);
 
 template <class F, class ABI>
 static int gntt_host(zk_ctx* ctx, ABI* pts, uint32_t log_n, int dir) {
@@ -355,12 +358,14 @@ static int gntt_host(zk_ctx* ctx, ABI* pts, uint32_t log_n, int dir) {
   return ZK_OK;
 }
 
-// out[j] = sum over column j of val_e L[row_e], j < V, as canonical ABI words
-// in host memory.  cp / row / cval: the matrix in CSC (cval empty: all ones).
+// out[j] = sum over column j of val_e L[row_e], j < V, as device affine points
+// handed to sink, which returns with the stream idle (the host vectors and the
+// buffers die after it).  cp / row / cval: the matrix in CSC (cval empty: all
+// ones).
 template <class F>
 static void colsum_points(zk_ctx* ctx, uint64_t V, const std::vector<uint64_t>& cp, const std::vector<uint32_t>& row,
                           const std::vector<zk_fr>& cval, bool unit, const Affine<typename GnField<F>::Raw>* d_L,
-                          void* host_out, const char* phase) {
+                          const char* phase, const std::function<void(const void*)>& sink) {
   using Raw = typename GnField<F>::Raw;
   using X = XYZZ<Raw>;
   using A = Affine<Raw>;
@@ -406,7 +411,7 @@ static void colsum_points(zk_ctx* ctx, uint64_t V, const std::vector<uint64_t>& 
   ZK_LAUNCH_CHECK();
   batch_normalize<typename GnField<F>::C>(d_out.as<X>(), V, d_pre.as<Raw>(), d_aff.as<A>(), st);
   ctx->prof.end(st, pi);
-  affine_to_host<F>(ctx, d_aff.as<A>(), V, host_out);   // synchronises: the host vectors and buffers die after it
+  sink(d_aff.p);
 }
 
 bool same_g1(const zk_g1_affine& a, const zk_g1_affine& b) {
@@ -428,9 +433,137 @@ void generators(zk_ctx* ctx, zk_g1_affine& g1, zk_g2_affine& g2) {
 }
 
 // ------------------------------------------------------------ the key ---
+// The halves of zk_groth16_setup_srs_sound, shared with the prepared strings
+// (lagrange.hip).  Upper half, circuit-independent:
+void srs_lagrange_transforms(zk_ctx* ctx, const zk_srs* srs, uint32_t log_n, void* d_abi, G1A* L1, G2A* L2) {
+  const uint64_t n = 1ull << log_n;
+  const zk_g1_affine* g1src[3] = {srs->tau_g1, srs->alpha_tau_g1, srs->beta_tau_g1};
+  const char* g1name[3] = {"srs_ntt_g1_tau", "srs_ntt_g1_alpha", "srs_ntt_g1_beta"};
+  for (int k = 0; k < 3; k++) {
+    chunked_copy(ctx, d_abi, g1src[k], n, sizeof(zk_g1_affine), hipMemcpyHostToDevice);
+    gntt_device<FqC>(ctx, static_cast<const uint64_t*>(d_abi), log_n, true, L1 + k * n, g1name[k]);
+  }
+  chunked_copy(ctx, d_abi, srs->tau_g2, n, sizeof(zk_g2_affine), hipMemcpyHostToDevice);
+  gntt_device<Fq2C>(ctx, static_cast<const uint64_t*>(d_abi), log_n, true, L2, "srs_ntt_g2");
+}
+
+void srs_hdiff(zk_ctx* ctx, const zk_g1_affine* tau_g1, uint64_t n, void* d_abi, G1A* d_out) {
+  hipStream_t st = ctx->stream;
+  DevBuf d_x, d_pre;
+  d_x.ensure(sizeof(G1X) * n);
+  d_pre.ensure(sizeof(Fq) * n);
+  chunked_copy(ctx, d_abi, tau_g1, 2 * n, sizeof(zk_g1_affine), hipMemcpyHostToDevice);
+  const int pi = ctx->prof.begin(st, "srs_hdiff", n);
+  k_gn_hdiff<<<ceil_div(n, GN_BLOCK), GN_BLOCK, 0, st>>>(static_cast<const uint64_t*>(d_abi), n, d_x.as<G1X>());
+  ZK_LAUNCH_CHECK();
+  batch_normalize<G1>(d_x.as<G1X>(), n, d_pre.as<Fq>(), d_out, st);
+  ctx->prof.end(st, pi);
+  ZK_HIP(hipStreamSynchronize(st));   // d_x / d_pre die here
+}
+
+// Lower half: the four column sums of the circuit over the Lagrange points.
+void srs_column_sums(zk_ctx* ctx, const zk_r1cs_csr* q, uint64_t n, const G1A* L1, const G2A* L2,
+                     const SrsSumSink& sink) {
+  const uint64_t V = q->num_variables, nc = q->num_constraints;
+  {
+    std::vector<uint64_t> cp;
+    std::vector<uint32_t> row;
+    std::vector<zk_fr> cval;
+    {
+      HostPhase hp(ctx->prof, "srs_csc_host");
+      csr_to_csc(nc, V, q->a_rowptr, q->a_col, q->a_val, cp, row, cval);
+    }
+    colsum_points<FqC>(ctx, V, cp, row, cval, !q->a_val, L1, "srs_colsum_a_g1",
+                       [&](const void* d) { sink(SRS_SUM_A, d); });
+    {
+      HostPhase hp(ctx->prof, "srs_csc_host");
+      csr_to_csc(nc, V, q->b_rowptr, q->b_col, q->b_val, cp, row, cval);
+    }
+    colsum_points<FqC>(ctx, V, cp, row, cval, !q->b_val, L1, "srs_colsum_b_g1",
+                       [&](const void* d) { sink(SRS_SUM_B1, d); });
+    colsum_points<Fq2C>(ctx, V, cp, row, cval, !q->b_val, L2, "srs_colsum_b_g2",
+                        [&](const void* d) { sink(SRS_SUM_B2, d); });
+  }
+  {
+    // ic: one matrix of 3 n rows over [L | alpha L | beta L] -- C's rows, then
+    // B's from n, then A's from 2 n
+    const uint64_t* rps[3] = {q->c_rowptr, q->b_rowptr, q->a_rowptr};
+    const uint32_t* cols[3] = {q->c_col, q->b_col, q->a_col};
+    const zk_fr* vals[3] = {q->c_val, q->b_val, q->a_val};
+    const bool unit = !vals[0] && !vals[1] && !vals[2];
+    std::vector<uint64_t> cp;
+    std::vector<uint32_t> row;
+    std::vector<zk_fr> cval;
+    {
+      HostPhase hp(ctx->prof, "srs_csc_host");
+      std::vector<uint64_t> rp(3 * n + 1, 0);
+      std::vector<uint32_t> col;
+      std::vector<zk_fr> val;
+      const zk_fr one = {{1, 0, 0, 0}};
+      for (int m = 0; m < 3; m++) {
+        const uint64_t nnz = nc ? rps[m][nc] : 0;
+        for (uint64_t i = 0; i < n; i++) rp[m * n + i + 1] = col.size() + (nc ? rps[m][std::min(i + 1, nc)] : 0);
+        col.insert(col.end(), cols[m], cols[m] + nnz);
+        if (!unit) {
+          if (vals[m]) val.insert(val.end(), vals[m], vals[m] + nnz);
+          else val.insert(val.end(), nnz, one);
+        }
+      }
+      csr_to_csc(3 * n, V, rp.data(), col.data(), unit ? nullptr : val.data(), cp, row, cval);
+    }
+    colsum_points<FqC>(ctx, V, cp, row, cval, unit, L1, "srs_colsum_ic", [&](const void* d) { sink(SRS_SUM_IC, d); });
+  }
+}
+
+// the fixed points and lengths of a key from a string (delta = gamma = 1)
+void srs_key_header(const zk_g1_affine& alpha_g1, const zk_g1_affine& beta_g1, const zk_g2_affine& beta_g2,
+                    const zk_g1_affine& g1, const zk_g2_affine& g2, uint64_t V, uint64_t n, uint64_t num_public,
+                    zk_pk* pk, zk_vk* vk) {
+  if (vk) {
+    vk->alpha_g1 = alpha_g1;
+    vk->beta_g2 = beta_g2;
+    vk->gamma_g2 = g2;
+    vk->delta_g2 = g2;
+    vk->num_public = num_public;
+    vk->ic_len = num_public + 1;
+  }
+  if (pk) {
+    pk->alpha_g1 = alpha_g1;
+    pk->beta_g1 = beta_g1;
+    pk->delta_g1 = g1;
+    pk->beta_g2 = beta_g2;
+    pk->delta_g2 = g2;
+    pk->num_public = num_public;
+    pk->a_len = V;
+    pk->b_len = V;
+    pk->b2_len = V;
+    pk->ic_len = V - num_public - 1;
+    pk->h_len = n;
+  }
+}
+
+void SrsHostKey::take(zk_ctx* ctx, int which, const void* d) {
+  if (which == SRS_SUM_B2) {
+    affine_to_host<Fq2C>(ctx, static_cast<const G2A*>(d), b2.size(), b2.data());
+    return;
+  }
+  std::vector<zk_g1_affine>& out = which == SRS_SUM_A ? a1 : which == SRS_SUM_B1 ? b1 : ic;
+  affine_to_host<FqC>(ctx, static_cast<const G1A*>(d), out.size(), out.data());
+}
+void SrsHostKey::fill(const zk_g1_affine& alpha_g1, const zk_g1_affine& beta_g1, const zk_g2_affine& beta_g2,
+                      const zk_g1_affine& g1, const zk_g2_affine& g2, uint64_t num_public, zk_pk* pk, zk_vk* vk) const {
+  const uint64_t V = a1.size(), n = h.size(), nic = V - num_public - 1, nvk = num_public + 1;
+  srs_key_header(alpha_g1, beta_g1, beta_g2, g1, g2, V, n, num_public, pk, vk);
+  if (vk) std::memcpy(vk->ic_g1, ic.data(), sizeof(zk_g1_affine) * nvk);
+  std::memcpy(pk->a_g1, a1.data(), sizeof(zk_g1_affine) * V);
+  std::memcpy(pk->b_g1, b1.data(), sizeof(zk_g1_affine) * V);
+  std::memcpy(pk->b_g2, b2.data(), sizeof(zk_g2_affine) * V);
+  if (nic) std::memcpy(pk->ic_g1, ic.data() + nvk, sizeof(zk_g1_affine) * nic);
+  std::memcpy(pk->h_g1, h.data(), sizeof(zk_g1_affine) * n);
+}
+
 static int setup_srs(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_srs* srs, uint64_t num_public, zk_pk* pk, zk_vk* vk) {
   Range range("zk_setup_srs");
-  hipStream_t st = ctx->stream;
   const uint64_t V = q->num_variables, nc = q->num_constraints;
   if (num_public >= V) return ZK_ERR_SETUP_PARAMS;
   if (nc > (1ull << 32) || srs->log_n > 31) return ZK_ERR_DOMAIN;
@@ -443,110 +576,34 @@ static int setup_srs(zk_ctx* ctx, const zk_r1cs_csr* q, const zk_srs* srs, uint6
                std::to_string(N) + " (or its arrays are shorter than log_n states)";
     return ZK_ERR_DOMAIN;
   }
-  // three blocks of n rows in one u32 index (the mixed ic sum below)
+  // three blocks of n rows in one u32 index (the mixed ic sum)
   if (V >= 0x80000000ull || n > 0x40000000ull) return ZK_ERR_ARG;
   if (same_g1(srs->tau_g1[n], srs->tau_g1[0])) {
     ctx->err = "sound setup: tau lies on the evaluation domain (Z(tau) = 0)";
     return ZK_ERR_SETUP_PARAMS;
   }
-  const uint64_t nic = V - num_public - 1, nvk = num_public + 1;
 
   // ---- [L_i]_1, [alpha L_i]_1, [beta L_i]_1 back to back, and [L_i]_2 ----
   DevBuf d_abi, L1, L2;
   d_abi.ensure(std::max(sizeof(zk_g1_affine) * 2 * n, sizeof(zk_g2_affine) * n));
   L1.ensure(sizeof(G1A) * 3 * n);
   L2.ensure(sizeof(G2A) * n);
-  const zk_g1_affine* g1src[3] = {srs->tau_g1, srs->alpha_tau_g1, srs->beta_tau_g1};
-  const char* g1name[3] = {"srs_ntt_g1_tau", "srs_ntt_g1_alpha", "srs_ntt_g1_beta"};
-  for (int k = 0; k < 3; k++) {
-    chunked_copy(ctx, d_abi.p, g1src[k], n, sizeof(zk_g1_affine), hipMemcpyHostToDevice);
-    gntt_device<FqC>(ctx, d_abi.as<uint64_t>(), log_n, true, L1.as<G1A>() + k * n, g1name[k]);
-  }
-  chunked_copy(ctx, d_abi.p, srs->tau_g2, n, sizeof(zk_g2_affine), hipMemcpyHostToDevice);
-  gntt_device<Fq2C>(ctx, d_abi.as<uint64_t>(), log_n, true, L2.as<G2A>(), "srs_ntt_g2");
+  srs_lagrange_transforms(ctx, srs, log_n, d_abi.p, L1.as<G1A>(), L2.as<G2A>());
 
   // ---- everything into scratch: the keys change only once nothing can fail ----
-  std::vector<zk_g1_affine> a1(V), b1(V), ic(V), h(n);
-  std::vector<zk_g2_affine> b2(V);
+  SrsHostKey key(V, n);
+  srs_column_sums(ctx, q, n, L1.as<G1A>(), L2.as<G2A>(), [&](int which, const void* d) { key.take(ctx, which, d); });
   {
-    std::vector<uint64_t> cp;
-    std::vector<uint32_t> row;
-    std::vector<zk_fr> cval;
-    csr_to_csc(nc, V, q->a_rowptr, q->a_col, q->a_val, cp, row, cval);
-    colsum_points<FqC>(ctx, V, cp, row, cval, !q->a_val, L1.as<G1A>(), a1.data(), "srs_colsum_a_g1");
-    csr_to_csc(nc, V, q->b_rowptr, q->b_col, q->b_val, cp, row, cval);
-    colsum_points<FqC>(ctx, V, cp, row, cval, !q->b_val, L1.as<G1A>(), b1.data(), "srs_colsum_b_g1");
-    colsum_points<Fq2C>(ctx, V, cp, row, cval, !q->b_val, L2.as<G2A>(), b2.data(), "srs_colsum_b_g2");
-  }
-  {
-    // ic: one matrix of 3 n rows over [L | alpha L | beta L] -- C's rows, then
-    // B's from n, then A's from 2 n
-    const uint64_t* rps[3] = {q->c_rowptr, q->b_rowptr, q->a_rowptr};
-    const uint32_t* cols[3] = {q->c_col, q->b_col, q->a_col};
-    const zk_fr* vals[3] = {q->c_val, q->b_val, q->a_val};
-    const bool unit = !vals[0] && !vals[1] && !vals[2];
-    std::vector<uint64_t> rp(3 * n + 1, 0);
-    std::vector<uint32_t> col;
-    std::vector<zk_fr> val;
-    const zk_fr one = {{1, 0, 0, 0}};
-    for (int m = 0; m < 3; m++) {
-      const uint64_t nnz = nc ? rps[m][nc] : 0;
-      for (uint64_t i = 0; i < n; i++) rp[m * n + i + 1] = col.size() + (nc ? rps[m][std::min(i + 1, nc)] : 0);
-      col.insert(col.end(), cols[m], cols[m] + nnz);
-      if (!unit) {
-        if (vals[m]) val.insert(val.end(), vals[m], vals[m] + nnz);
-        else val.insert(val.end(), nnz, one);
-      }
-    }
-    std::vector<uint64_t> cp;
-    std::vector<uint32_t> row;
-    std::vector<zk_fr> cval;
-    csr_to_csc(3 * n, V, rp.data(), col.data(), unit ? nullptr : val.data(), cp, row, cval);
-    colsum_points<FqC>(ctx, V, cp, row, cval, unit, L1.as<G1A>(), ic.data(), "srs_colsum_ic");
-  }
-  {
-    DevBuf d_x, d_pre, d_aff;
-    d_x.ensure(sizeof(G1X) * n);
-    d_pre.ensure(sizeof(Fq) * n);
+    DevBuf d_aff;
     d_aff.ensure(sizeof(G1A) * n);
-    chunked_copy(ctx, d_abi.p, srs->tau_g1, 2 * n, sizeof(zk_g1_affine), hipMemcpyHostToDevice);
-    const int pi = ctx->prof.begin(st, "srs_hdiff", n);
-    k_gn_hdiff<<<ceil_div(n, GN_BLOCK), GN_BLOCK, 0, st>>>(d_abi.as<uint64_t>(), n, d_x.as<G1X>());
-    ZK_LAUNCH_CHECK();
-    batch_normalize<G1>(d_x.as<G1X>(), n, d_pre.as<Fq>(), d_aff.as<G1A>(), st);
-    ctx->prof.end(st, pi);
-    affine_to_host<FqC>(ctx, d_aff.as<G1A>(), n, h.data());
+    srs_hdiff(ctx, srs->tau_g1, n, d_abi.p, d_aff.as<G1A>());
+    affine_to_host<FqC>(ctx, d_aff.as<G1A>(), n, key.h.data());
   }
   zk_g1_affine g1;
   zk_g2_affine g2;
   generators(ctx, g1, g2);
   if (ctx->prof.on) ctx->prof.collect();
-
-  if (vk) {
-    vk->alpha_g1 = srs->alpha_tau_g1[0];
-    vk->beta_g2 = srs->beta_g2;
-    vk->gamma_g2 = g2;
-    vk->delta_g2 = g2;
-    vk->num_public = num_public;
-    vk->ic_len = nvk;
-    std::memcpy(vk->ic_g1, ic.data(), sizeof(zk_g1_affine) * nvk);
-  }
-  pk->alpha_g1 = srs->alpha_tau_g1[0];
-  pk->beta_g1 = srs->beta_tau_g1[0];
-  pk->delta_g1 = g1;
-  pk->beta_g2 = srs->beta_g2;
-  pk->delta_g2 = g2;
-  pk->num_public = num_public;
-  pk->a_len = V;
-  pk->b_len = V;
-  pk->b2_len = V;
-  pk->ic_len = nic;
-  pk->h_len = n;
-  std::memcpy(pk->a_g1, a1.data(), sizeof(zk_g1_affine) * V);
-  std::memcpy(pk->b_g1, b1.data(), sizeof(zk_g1_affine) * V);
-  std::memcpy(pk->b_g2, b2.data(), sizeof(zk_g2_affine) * V);
-  if (nic) std::memcpy(pk->ic_g1, ic.data() + nvk, sizeof(zk_g1_affine) * nic);
-  std::memcpy(pk->h_g1, h.data(), sizeof(zk_g1_affine) * n);
+  key.fill(srs->alpha_tau_g1[0], srs->beta_tau_g1[0], srs->beta_g2, g1, g2, num_public, pk, vk);
   return ZK_OK;
 }
 
@@ -591,7 +648,7 @@ static int srs_generate(zk_ctx* ctx, uint32_t log_n, const zk_fr* tau, const zk_
 // One array through the point validation; the identity is refused too.  true
 // when every entry is valid; rc: ZK_OK or the call's own failure.
 template <class P>
-static bool srs_valid(zk_ctx* ctx, const char* name, const P* pts, size_t n, int& rc) {
+bool srs_valid(zk_ctx* ctx, const char* name, const P* pts, size_t n, int& rc) {
   std::vector<uint8_t> st(n);
   size_t bad = n;
   if constexpr (sizeof(P) == sizeof(zk_g1_affine)) rc = zk_g1_validate(ctx, pts, n, st.data(), &bad);
@@ -609,6 +666,8 @@ static bool srs_valid(zk_ctx* ctx, const char* name, const P* pts, size_t n, int
     }
   return true;
 }
+template bool srs_valid<zk_g1_affine>(zk_ctx*, const char*, const zk_g1_affine*, size_t, int&);
+template bool srs_valid<zk_g2_affine>(zk_ctx*, const char*, const zk_g2_affine*, size_t, int&);
 static bool negated_g1(const zk_g1_affine& p, zk_g1_affine& out) {
   host::A1 a;
   if (!host::load(p, a)) return false;

@@ -8,6 +8,10 @@
 // here for both groups): beside the accumulator only the formula's own values
 // are live, which is what lets the G2 walk fit without spills.
 #pragma once
+#include <chrono>
+#include <functional>
+#include <vector>
+
 #include "ceremony.hpp"
 
 namespace zk {
@@ -187,5 +191,53 @@ bool same_g1(const zk_g1_affine& a, const zk_g1_affine& b);
 bool same_g2(const zk_g2_affine& a, const zk_g2_affine& b);
 void generators(zk_ctx* ctx, zk_g1_affine& g1, zk_g2_affine& g2);
 bool pairs_equal(const zk_g1_affine& a, const zk_g2_affine& p, const zk_g1_affine& b, const zk_g2_affine& q);
+
+// wall time of a host-side phase into the profiler
+struct HostPhase {
+  Prof& prof;
+  const char* name;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  HostPhase(Prof& p, const char* nm) : prof(p), name(nm) {}
+  ~HostPhase() {
+    prof.add_host(name, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  }
+};
+
+// ---- the halves of zk_groth16_setup_srs_sound, shared with the prepared
+// strings (lagrange.hip) ------------------------------------------------------
+// n device affine points -> canonical ABI words in host memory, through
+// gn_points_to_abi and chunked_copy (synchronises)
+template <class F>
+void affine_to_host(zk_ctx* ctx, const Affine<typename GnField<F>::Raw>* d_in, size_t n, void* host_out);
+// One array through the point validation; the identity is refused too (srs.hip)
+template <class P>
+bool srs_valid(zk_ctx* ctx, const char* name, const P* pts, size_t n, int& rc);
+// Upper half: the four inverse transforms of the string's first n = 2^log_n
+// powers -> L1 = [L | alpha L | beta L]_1 (3 n points), L2 = [L]_2.  d_abi:
+// device scratch of max(2 n G1, n G2) ABI points.
+void srs_lagrange_transforms(zk_ctx* ctx, const zk_srs* srs, uint32_t log_n, void* d_abi, G1A* L1, G2A* L2);
+// d_out[i] = tau_g1[i + n] - tau_g1[i], i < n, affine (d_abi as above; synchronises)
+void srs_hdiff(zk_ctx* ctx, const zk_g1_affine* tau_g1, uint64_t n, void* d_abi, G1A* d_out);
+// Lower half: the circuit's column sums over L1 / L2, num_variables device
+// affine points each, handed to sink one after the other (A, B1, B2 in G2, IC:
+// vk entries first); sink returns with the stream idle, the points die after it.
+enum { SRS_SUM_A = 0, SRS_SUM_B1, SRS_SUM_B2, SRS_SUM_IC };
+using SrsSumSink = std::function<void(int which, const void* d_points)>;
+void srs_column_sums(zk_ctx* ctx, const zk_r1cs_csr* q, uint64_t n, const G1A* L1, const G2A* L2,
+                     const SrsSumSink& sink);
+// the fixed points and the lengths of a key from a string (gamma = delta = 1);
+// pk, vk: either may be null
+void srs_key_header(const zk_g1_affine& alpha_g1, const zk_g1_affine& beta_g1, const zk_g2_affine& beta_g2,
+                    const zk_g1_affine& g1, const zk_g2_affine& g2, uint64_t V, uint64_t n, uint64_t num_public,
+                    zk_pk* pk, zk_vk* vk);
+// A host key in scratch: the caller's keys change only once nothing can fail
+struct SrsHostKey {
+  std::vector<zk_g1_affine> a1, b1, ic, h;
+  std::vector<zk_g2_affine> b2;
+  SrsHostKey(uint64_t V, uint64_t n) : a1(V), b1(V), ic(V), h(n), b2(V) {}
+  void take(zk_ctx* ctx, int which, const void* d_points);   // one of srs_column_sums' results
+  void fill(const zk_g1_affine& alpha_g1, const zk_g1_affine& beta_g1, const zk_g2_affine& beta_g2,
+            const zk_g1_affine& g1, const zk_g2_affine& g2, uint64_t num_public, zk_pk* pk, zk_vk* vk) const;
+};
 
 }  // namespace zk

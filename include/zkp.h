@@ -1145,9 +1145,60 @@ int zk_srs_digest(const zk_srs *srs, uint8_t out[32]);                          
  * (the vk's alpha_g1, beta_g2 and delta_g2 are the pk's).  Host only. */
 int zk_groth16_key_digest_sound(const zk_pk *pk, const zk_vk *vk, uint8_t out[32]);                /* host */
 
+/* ---------------------------------------------------------- tree digests --- */
+/* The two digests above are one SHA-256 chain over every point: serial by
+ * definition, on one host thread.  V2 is a second definition of the same two
+ * challenges, parallel by construction: leaves of 256 points hashed
+ * independently -- one GPU lane per leaf (csrc/digest.hpp) -- and one short
+ * host hash over the leaf digests.  V1, its bytes and its calls stay as they
+ * are; V2 is what a ceremony opts into, and ONE CEREMONY USES ONE VERSION
+ * THROUGHOUT (a proof made over one version's challenge is REJECT under the
+ * other's).  No reference counterpart.
+ *
+ * enc = zk_g1_compress / zk_g2_compress, byte for byte, including what they
+ * write for an infinity byte that is non-zero but not 1 (the identity, 0xc0 and
+ * zeros, whatever the coordinates hold), for junk coordinates and for
+ * non-canonical words: the encoder does not validate, and neither does the
+ * device.
+ *
+ *   LEAF = 256 points.
+ *   leaf(g, P[0..m)), 1 <= m <= 256, g = 1 (G1) or 2 (G2):
+ *       SHA-256( B0 | enc(P[0]) | ... | enc(P[m-1]) )
+ *       B0 = 64 bytes: "ZKAMD-LEAF-V2" (13) | byte(g) | be16(m) | 48 zero bytes
+ *   leaves(g, arr, n) = leaf(g, arr[256 j .. min(n, 256 j + 256))) for j = 0 .. ceil(n/256)-1,
+ *                       concatenated; nothing for n = 0.
+ *
+ *   SRS V2 = SHA-256( "ZKAMD-SRS-V2" | the five be64 of V1 | enc(beta_g2)
+ *                     | leaves(1,tau_g1) | leaves(2,tau_g2) | leaves(1,alpha_tau_g1) | leaves(1,beta_tau_g1) )
+ *   KEY V2 = SHA-256( "ZKAMD-KEY-V2" | the seven be64 of V1
+ *                     | enc(alpha_g1) | enc(beta_g1) | enc(delta_g1) | enc(beta_g2) | enc(delta_g2) | enc(vk gamma_g2)
+ *                     | leaves(1,a_g1) | leaves(1,b_g1) | leaves(2,b_g2) | leaves(1,ic_g1) | leaves(1,h_g1) | leaves(1,vk ic_g1) )
+ *
+ * The 64-byte B0 puts the points on a block boundary (four G1 encodings, or
+ * two G2 encodings, are then exactly three blocks) and keeps a leaf apart
+ * from a top hash; the header's lengths and the order of the leaf digests fix
+ * every leaf's place.  At 2^20 constraints a top hash covers under 2 MB.
+ *
+ * The leaf digests of n points: 32 ceil(n / 256) bytes at out.  ctx == NULL
+ * selects the host twin -- the same definition in plain C++ -- so that a
+ * verifier without a GPU reaches the same bytes; with a ctx EVERY array goes
+ * through the GPU, whatever its length (there is no size rule), in chunks of
+ * ZK_OPT_POINT_CHUNK points rounded down to a multiple of 256 (at least 256).
+ * n == 0 -> ZK_OK, nothing written. */
+int zk_g1_leaf_digests(zk_ctx *ctx /* NULL: host */, const zk_g1_affine *pts, size_t n, uint8_t *out);
+int zk_g2_leaf_digests(zk_ctx *ctx /* NULL: host */, const zk_g2_affine *pts, size_t n, uint8_t *out);
+/* The V2 challenges: zk_srs_digest's / zk_groth16_key_digest_sound's argument
+ * checks (a NULL array with a non-zero length -> ZK_ERR_ARG); ctx == NULL: host. */
+int zk_srs_digest_v2(zk_ctx *ctx /* NULL: host */, const zk_srs *srs, uint8_t out[32]);
+int zk_groth16_key_digest_v2_sound(zk_ctx *ctx /* NULL: host */, const zk_pk *pk, const zk_vk *vk, uint8_t out[32]);
+
 /* Phase 1: the three proofs of one zk_srs_contribute(before, s, a, b), roles
  * TAU, ALPHA, BETA, challenge zk_srs_digest(before).  Host only; the shares as
- * zk_srs_contribute takes them (zero or >= r -> ZK_ERR_ARG). */
+ * zk_srs_contribute takes them (zero or >= r -> ZK_ERR_ARG).  A V2 ceremony
+ * needs no call of its own: zk_pok_make and zk_pok_verify_many take any
+ * 32-byte challenge, so its three proofs are zk_pok_make over
+ * zk_srs_digest_v2(before) with the same roles, and the check below takes
+ * that digest in before_digests. */
 typedef struct { zk_pok tau, alpha, beta; } zk_srs_contribution_proof;
 int zk_srs_prove_contribution(const zk_srs *before, const zk_fr *s, const zk_fr *a, const zk_fr *b,
                               zk_srs_contribution_proof *out);                                     /* host */

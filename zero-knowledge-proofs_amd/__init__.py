@@ -67,6 +67,7 @@ EXPORTS = (
     "zk_sha256", "zk_hash_to_g2_host", "zk_hash_to_g2", "zk_pok_make", "zk_pok_verify", "zk_pok_verify_many",
     "zk_srs_digest", "zk_groth16_key_digest_sound", "zk_srs_prove_contribution",
     "zk_srs_verify_contribution_proofs",
+    "zk_g1_leaf_digests", "zk_g2_leaf_digests", "zk_srs_digest_v2", "zk_groth16_key_digest_v2_sound",
     "zk_vk_prepare", "zk_vk_dev_free", "zk_vk_dev_bytes", "zk_vk_dev_is_sound", "zk_groth16_prepare_inputs",
     "zk_groth16_verify_many_prepared", "zk_groth16_verify_many_bytes_prepared",
     "zk_groth16_verify_key_srs_sound",
@@ -1068,6 +1069,16 @@ class Context:
         return self._hash_to_g2(test_lib().zk_test_hash_to_g2_capped, "zk_test_hash_to_g2_capped", msgs, dst,
                                 C.c_uint32(int(max_tries)))
 
+    def g1_leaf_digests(self, points):
+        """zk_g1_leaf_digests on the GPU: (n, 13) affine words -> a
+        (ceil(n / 256), 32) uint8 array, the V2 leaf digests (include/zkp.h,
+        "tree digests"), one lane per leaf of 256 points."""
+        return _leaf_digests(self, "zk_g1_leaf_digests", points, G1_WORDS)
+
+    def g2_leaf_digests(self, points):
+        """zk_g2_leaf_digests on the GPU: (n, 25) affine words -> leaf digests."""
+        return _leaf_digests(self, "zk_g2_leaf_digests", points, G2_WORDS)
+
     def pok_verify_many(self, poks, roles, challenges):
         """zk_pok_verify_many: n proofs ((n, 38) words: s_g1 then s_r), their
         roles (ZK_POK_*) and 32-byte challenges -> (n uint8 ZK_POK_* statuses,
@@ -1755,6 +1766,32 @@ def hash_to_g2_host(msg, dst):
     return out, tries.value
 
 
+def _leaf_digests(ctx, name, points, words):
+    a = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, words)
+    out = np.zeros((-(-len(a) // 256), 32), dtype=np.uint8)
+    rc = getattr(lib(), name)(C.c_void_p(ctx._h) if ctx is not None else None, _p(a) if len(a) else None,
+                              C.c_size_t(len(a)), _p(out) if len(a) else None)
+    _check(rc, ctx, name)
+    return out
+
+
+def g1_leaf_digests_host(points):
+    """zk_g1_leaf_digests with ctx == NULL: the host twin of
+    Context.g1_leaf_digests, the same bytes without a GPU."""
+    return _leaf_digests(None, "zk_g1_leaf_digests", points, G1_WORDS)
+
+
+def g2_leaf_digests_host(points):
+    """zk_g2_leaf_digests with ctx == NULL."""
+    return _leaf_digests(None, "zk_g2_leaf_digests", points, G2_WORDS)
+
+
+def _digest_version(version, what):
+    if version not in (1, 2):
+        raise ValueError(f"{what}: digest version {version!r} does not exist (1 or 2)")
+    return version
+
+
 def _pok_c(pok):
     w = np.ascontiguousarray(pok, dtype=np.uint64).reshape(POK_WORDS)
     return _Pok.from_buffer_copy(w.tobytes())
@@ -1977,31 +2014,44 @@ class CRS:
         return st.value == ZK_KEYSRS_OK, st.value
 
     # ---- phase-2 contributions with a proof of knowledge ----
-    def digest(self):
-        """zk_groth16_key_digest_sound: SHA-256 over the key's compressed points
-        (layout: include/zkp.h) -> 32 bytes; the challenge of the next
-        contribution's proof."""
+    def digest(self, ctx=None, version=1):
+        """The challenge of the next contribution's proof -> 32 bytes (layouts:
+        include/zkp.h).  version 1: zk_groth16_key_digest_sound, one SHA-256
+        over the key's compressed points on the host (ctx is not used).
+        version 2: zk_groth16_key_digest_v2_sound, the tree digest -- leaves
+        of 256 points hashed on the GPU when a ctx is given, by the host twin
+        otherwise, the same bytes either way.  One ceremony uses one version."""
         out = np.zeros(32, dtype=np.uint8)
-        _check(lib().zk_groth16_key_digest_sound(C.byref(self.pk._bind()), C.byref(self.vk.s), _p(out)), None,
-               "zk_groth16_key_digest_sound")
+        if _digest_version(version, "CRS.digest") == 1:
+            _check(lib().zk_groth16_key_digest_sound(C.byref(self.pk._bind()), C.byref(self.vk.s), _p(out)), None,
+                   "zk_groth16_key_digest_sound")
+        else:
+            _check(lib().zk_groth16_key_digest_v2_sound(C.c_void_p(ctx._h) if ctx is not None else None,
+                                                        C.byref(self.pk._bind()), C.byref(self.vk.s), _p(out)), ctx,
+                   "zk_groth16_key_digest_v2_sound")
         return out.tobytes()
 
-    def contribute_proved(self, ctx, d):
+    def contribute_proved(self, ctx, d, digest_version=1):
         """contribute(ctx, d) and the contributor's proof that they know d:
-        -> (new_crs, proof), proof = pok_make(d, ZK_POK_DELTA, self.digest())."""
+        -> (new_crs, proof), proof = pok_make(d, ZK_POK_DELTA, challenge) with
+        challenge = self.digest() (digest_version 1) or the tree digest
+        self.digest(ctx, 2) (digest_version 2)."""
+        _digest_version(digest_version, "CRS.contribute_proved")
         new = self.contribute(ctx, d)
-        return new, pok_make(d, ZK_POK_DELTA, self.digest())
+        return new, pok_make(d, ZK_POK_DELTA, self.digest(ctx, digest_version))
 
     @staticmethod
-    def verify_contribution_proof(ctx, before, after, proof):
+    def verify_contribution_proof(ctx, before, after, proof, digest_version=1):
         """Does `proof` show knowledge of the share that took delta from
         `before` to `after`? -> (ok, status): zk_pok_verify_many on the proof
-        with the digest of `before`, then the link
+        with the digest of `before` (digest_version: the version the ceremony
+        uses, as in contribute_proved), then the link
         e(s_g1, delta_2 before) e(-g1, delta_2 after) = 1 through
         pairing_products (a failed link is ZK_POK_REJECT).  It does not replace
         CRS.verify_contribution: a full audit runs both."""
+        _digest_version(digest_version, "CRS.verify_contribution_proof")
         pk = np.ascontiguousarray(proof, dtype=np.uint64).reshape(POK_WORDS)
-        st, _ = ctx.pok_verify_many(pk.reshape(1, -1), [ZK_POK_DELTA], [before.digest()])
+        st, _ = ctx.pok_verify_many(pk.reshape(1, -1), [ZK_POK_DELTA], [before.digest(ctx, digest_version)])
         if st[0] != ZK_POK_OK:
             return False, int(st[0])
         neg_g1 = np.array(to_limbs(G1_GENERATOR[0], 6) + to_limbs(FQ_MODULUS - G1_GENERATOR[1], 6) + [0],
@@ -2176,20 +2226,33 @@ class SRS:
         return st.value == ZK_SRSC_OK, st.value, sst.value
 
     # ---- contributions with proofs of knowledge ----
-    def digest(self):
-        """zk_srs_digest: SHA-256 over the string's compressed points (layout:
-        include/zkp.h) -> 32 bytes; the challenge of the next contribution's
-        proofs."""
+    def digest(self, ctx=None, version=1):
+        """The challenge of the next contribution's proofs -> 32 bytes (layouts:
+        include/zkp.h).  version 1: zk_srs_digest, one SHA-256 over the
+        string's compressed points on the host (ctx is not used).  version 2:
+        zk_srs_digest_v2, the tree digest -- leaves of 256 points hashed on
+        the GPU when a ctx is given, by the host twin otherwise, the same
+        bytes either way.  One ceremony uses one version."""
         out = np.zeros(32, dtype=np.uint8)
-        _check(lib().zk_srs_digest(C.byref(self._bind()), _p(out)), None, "zk_srs_digest")
+        if _digest_version(version, "SRS.digest") == 1:
+            _check(lib().zk_srs_digest(C.byref(self._bind()), _p(out)), None, "zk_srs_digest")
+        else:
+            _check(lib().zk_srs_digest_v2(C.c_void_p(ctx._h) if ctx is not None else None, C.byref(self._bind()),
+                                          _p(out)), ctx, "zk_srs_digest_v2")
         return out.tobytes()
 
-    def contribute_proved(self, ctx, s, a, b):
+    def contribute_proved(self, ctx, s, a, b, digest_version=1):
         """contribute(ctx, s, a, b) and the contributor's proofs that they know
         the shares -> (new_srs, share, proof): proof a (3, 38) array, the
         zk_pok of s, a, b with roles TAU, ALPHA, BETA and this string's
-        digest as the challenge (zk_srs_prove_contribution)."""
+        digest as the challenge (digest_version 1: zk_srs_prove_contribution;
+        2: pok_make over self.digest(ctx, 2), the tree digest)."""
+        _digest_version(digest_version, "SRS.contribute_proved")
         new, share = self.contribute(ctx, s, a, b)
+        if digest_version == 2:
+            ch = self.digest(ctx, 2)
+            return new, share, np.stack([pok_make(v, role, ch) for v, role in
+                                         ((s, ZK_POK_TAU), (a, ZK_POK_ALPHA), (b, ZK_POK_BETA))])
         pr = _SRSProof()
         _check(lib().zk_srs_prove_contribution(C.byref(self._bind()), C.byref(_fr(s)), C.byref(_fr(a)),
                                                C.byref(_fr(b)), C.byref(pr)), None, "zk_srs_prove_contribution")
